@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""bench.py -- SE(3) rollouts/s (horizon 30, batch 8192 per GPU) on N MI355X + roofline + CPU baseline.
+"""bench.py -- SE(3) rollouts/s (horizon 30, batch 8192 per GPU) on N MI355X.
 
-Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N > 1 it is launched by
-``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`` (one rank per GPU,
+Contract (driver): ``python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]``; for N > 1 it is
+launched by ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`` (one rank per GPU,
 RCCL).  Rank 0 prints ONE JSON line.
 
 A *step* is one pass of the hot path over one batch: the shooting-form rollout + running/terminal
@@ -11,20 +11,23 @@ cost + exact thrust gradient (SURVEY.md section 8d "canonical rollout", 4*(6N+10
 kernel.  The batch is fixed per GPU (weak scaling); the only cross-GPU exchange is ONE bucketed
 RCCL all-reduce(MIN) of the K packed (cost, index) keys at the end of the timed region
 (SURVEY.md section 8e).  Steps cycle through a ring of distinct input/output batches larger than the
-256 MiB Infinity Cache, so every step streams its operands from HBM.
+256 MiB Infinity Cache, so every step streams its operands from HBM.  The inputs come from a seeded
+generator: the same arguments give the same inputs on every run.
 
-Two legs time the same steps (SURVEY.md section 7 "report both"):
-  * primary (`value`, `roofline`): the steps are independent batches (a Monte-Carlo sweep, many
-    planners), so `--steps-per-launch` S = 64 of them go into ONE multi-batch kernel launch (grid.y);
-  * `single_launch`: one kernel launch per 8192-rollout step (sequentially dependent sampling
-    iterations of one planner): 6 MB per launch = 1 us of HBM time, i.e. latency-bound.
-Launches are captured once into a hipGraph and replayed inside the timed region.
+A plain run is the headline alone: set-up, W warm-up steps, exactly K timed steps, the result line
+(`value` = rollouts/s, `ms_per_step` = milliseconds per timed step).  The steps are independent batches
+(a Monte-Carlo sweep, many planners), so `--steps-per-launch` S = 64 of them go into ONE multi-batch
+kernel launch (grid.y); the K steps are floor(K / S) full launches plus one launch of the K mod S left
+over, captured into hipGraphs and replayed inside the timed region.  Before the timed region the device
+gets ~60 ms of untimed load of its own (`warm_device`): after the idle gap of a graph capture the card
+needs 20-40 ms before a kernel's duration settles.  `--dump-outputs DIR` then writes what the last
+timed step computed (cost, thrust gradient, fused argmin) as DIR/<name>.npy.
 
-The launch shape never depends on `--steps`: a *pass* is ceil(K / S) full S-batch launches, and the pass is
-repeated (`repeats`) until the timed region lasts at least `--min-ms` (20 ms), so a driver that asks for
-K = 20 steps measures the same steady state as K = 20000; `steps` echoes K, `steps_timed` is what ran,
-`ms_per_step` is the mean over the steps that ran.  Every device-time leg (the timed region included) is preceded by ~60 ms of
-its own load, untimed (`warm_device`): after the idle gap of a graph capture the card needs 20-40 ms before a kernel's duration settles.
+`--full` adds every other leg (SURVEY.md section 7 "report both"): the CPU baseline, the same K steps
+as one launch per step (`single_launch`: sequentially dependent sampling iterations of one planner,
+6 MB per launch = 1 us of HBM time, i.e. latency-bound), the p95 solve latency, the voxel map, the
+BASELINE config-2 / config-3 legs, the on-device iteration loop and the closed-loop Monte-Carlo; each
+`--no-<leg>` option drops one of them, `--sweep` adds saturating batch sizes.
 
 `--gpus N` with N > 1 and no torchrun environment: bench.py starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` itself, as a child process and BEFORE
@@ -43,14 +46,18 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBPS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (6.29 TB/s measured copy)
+HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E peak 8.0 TB/s (6.29 TB/s measured copy)
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20480)
-    ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=20480, help="timed steps (exactly this many)")
+    ap.add_argument("--warmup", type=int, default=200, help="untimed warm-up steps before them (rounded up to whole launches)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (CPU baseline, single_launch, solve, voxel map, configs, iteration loop, closed loop)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 64 MiB)")
     ap.add_argument("--batch", type=int, default=8192, help="rollouts per GPU per step (BASELINE.json metric: 8192)")
     ap.add_argument("--horizon", type=int, default=30)
     ap.add_argument("--ring", type=int, default=0, help="distinct batches cycled through (0 = enough to exceed 512 MiB)")
@@ -63,8 +70,8 @@ def parse():
                     help="independent 8192-rollout steps issued as ONE multi-batch kernel launch (1 = one launch per step)")
     ap.add_argument("--no-single", action="store_true", help="skip the one-launch-per-step leg")
     ap.add_argument("--variant", type=int, default=0, help="se3mpc_set_rollout_variant (0 = auto)")
-    ap.add_argument("--sweep", action="store_true", help="also time saturating batch sizes (extra keys)")
-    ap.add_argument("--min-ms", type=float, default=20.0, help="the pass of ceil(K/S) launches is repeated until the timed region lasts this long")
+    ap.add_argument("--sweep", action="store_true", help="with --full: also time saturating batch sizes (extra keys)")
+    ap.add_argument("--min-ms", type=float, default=20.0, help="--full legs: each timed pass is repeated until it lasts this long")
     ap.add_argument("--dry-run", action="store_true",
                     help="rank plumbing only, no HIP: spawn / rendezvous (gloo) / key all-reduce / JSON line with value null "
                          "(what the CPU test-suite runs to check that --gpus N really starts N ranks)")
@@ -72,8 +79,15 @@ def parse():
     ap.add_argument("--no-iterated", action="store_true", help="skip the on-device K-iteration leg")
     ap.add_argument("--no-closed-loop", action="store_true", help="skip the closed-loop Monte-Carlo leg")
     ap.add_argument("--iterated-ks", default="0,1,4,16,64", help="iteration counts of the on-device iteration leg (profiling: one value)")
-    ap.add_argument("--no-primary", action="store_true", help="profiling only: skip the rollout legs (no JSON line is printed)")
-    return ap.parse_args()
+    ap.add_argument("--no-primary", action="store_true", help="profiling only, with --full: skip the rollout legs (no JSON line is printed)")
+    a = ap.parse_args()
+    if (a.no_primary or a.sweep) and not a.full:
+        ap.error("--no-primary and --sweep select --full legs: add --full")
+    if a.no_primary and a.dump_outputs:
+        ap.error("--dump-outputs writes the timed rollout steps' outputs: it cannot go with --no-primary")
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    return a
 
 
 def make_ring(torch, dev, B, N, ring, seed):
@@ -173,21 +187,19 @@ def cpu_baseline(B, N, seconds):
                 host_cpus=os.cpu_count())
 
 
-def timed_region(torch, dist, world, dev, replays, graph, launch_all, keys, allreduce_min_keys):
-    """The contract's timed region: barrier + synchronize, `replays` x (the captured passes), [one bucketed
-    all-reduce(MIN) of the step keys], synchronize + barrier; MAX over ranks.  Returns (elapsed_s, device_ms
-    between the HIP events that bracket the launches on the launch stream)."""
+def timed_region(torch, dist, world, dev, runs, keys, allreduce_min_keys):
+    """The contract's timed region: barrier + synchronize, the K steps (`runs`: (graph replay or eager launches,
+    count) pairs), [one bucketed all-reduce(MIN) of the step keys], synchronize + barrier; MAX over ranks.  Returns
+    (elapsed_s, device_ms between the HIP events that bracket the launches on the launch stream)."""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     e0.record()
-    for _ in range(replays):
-        if graph is not None:
-            graph.replay()
-        else:
-            launch_all()
+    for fn, count in runs:
+        for _ in range(count):
+            fn()
     e1.record()
     if world > 1:
         allreduce_min_keys(keys)     # the single exchange: ONE bucketed all-reduce(MIN) of the packed step keys
@@ -249,16 +261,44 @@ def warm_device(torch, fn, ms=WARM_MS, chunk=4):
 MAX_GRAPH_NODES = 2048
 
 
-def timed_plan(K, per_launch, pass_ms, min_ms):
-    """How the timed region is built so that its launch shape never depends on K: a pass = ceil(K / per_launch)
-    FULL launches; `passes_per_graph` passes are captured into one hipGraph (at most MAX_GRAPH_NODES kernel
-    nodes), which is replayed `replays` times; passes x pass_ms >= min_ms."""
-    launches_per_pass = max(1, math.ceil(K / per_launch))
-    passes = max(1, math.ceil(min_ms / max(pass_ms, 1e-6)))
-    per_graph = max(1, min(passes, MAX_GRAPH_NODES // launches_per_pass))
-    replays = math.ceil(passes / per_graph)
-    return dict(launches_per_pass=launches_per_pass, steps_per_pass=launches_per_pass * per_launch,
-                passes_per_graph=per_graph, replays=replays, repeats=per_graph * replays)
+def timed_plan(K, per_launch, ring):
+    """How the K timed steps are laid out.  Step i runs on ring slot i mod `ring` (a multiple of per_launch), in
+    launches of per_launch consecutive steps.  When K reaches `chunk_steps` (whole ring cycles, at most
+    MAX_GRAPH_NODES full launches), one chunk is captured into a hipGraph and replayed `chunk_replays` times; the
+    `tail_steps` left over (fewer than a chunk) are one more graph of full launches plus, if K mod per_launch != 0,
+    one launch of that remainder.  chunk_replays x chunk_steps + tail_steps == K, always."""
+    cap = max(ring, MAX_GRAPH_NODES * per_launch // ring * ring)
+    chunk = cap if K >= cap else 0
+    replays = K // chunk if chunk else 0
+    tail = K - replays * chunk
+    return dict(chunk_steps=chunk, chunk_replays=replays, tail_steps=tail,
+                launches=replays * (chunk // per_launch) + math.ceil(tail / per_launch))
+
+
+DUMP_LIMIT = 64 * 2 ** 20
+
+
+def dump_outputs(ops, out_dir, cost, grad, key):
+    """What the last timed step computed, as a caller of the rollout path receives it: `cost` float32 (B,),
+    `grad` float32 (3N, B) (the thrust gradient in the kernel's lane layout), the fused batch argmin as
+    `argmin_index` / `argmin_cost` float64 (1,).  Above DUMP_LIMIT bytes a fixed, seeded sample of the B
+    rollouts is written instead, with its indices (`sample_index`).  -> {name: shape}"""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    idx, kc = ops.decode_key(key)
+    out = {}
+    B = cost.shape[0]
+    if 4 * B * (1 + grad.shape[0]) > DUMP_LIMIT - 4096:
+        m = (DUMP_LIMIT - 4096) // (4 * (1 + grad.shape[0]) + 8)
+        pick = np.sort(np.random.default_rng(0).choice(B, m, replace=False))
+        sel = torch.from_numpy(pick).to(cost.device)
+        cost, grad = cost[sel], grad[:, sel]
+        out["sample_index"] = pick.astype(np.float64)
+    out.update(cost=cost.float().cpu().numpy(), grad=grad.float().cpu().numpy(),
+               argmin_index=np.array([idx], np.float64), argmin_cost=np.array([kc], np.float64))
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return {name: list(v.shape) for name, v in out.items()}
 
 
 def spawn_ranks(a):
@@ -340,7 +380,7 @@ def main():
     if a.dry_run:
         return dry_run(a, rank, world)
     cpu_stats = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         # rank 0 only, also when several ranks run (the other ranks wait for it at the rendezvous, outside every timed region);
         # before any HIP call: it spawns worker processes
         cpu_stats = cpu_baseline(a.batch, a.horizon, a.cpu_seconds)
@@ -386,92 +426,78 @@ def main():
                                           grad[s0:s0 + n], wave_keys=wk[i0:i0 + n], index_base=base)
 
     def run_steps(nsteps, per_launch, fold=True):
-        """nsteps (a multiple of per_launch) steps as FULL launches of per_launch consecutive ring slots"""
-        assert nsteps % per_launch == 0 and ring % per_launch == 0
+        """steps 0 .. nsteps-1 (step i on ring slot i mod ring, wave keys in row i) as launches of per_launch
+        consecutive steps, the last one carrying the nsteps mod per_launch left over"""
+        assert ring % per_launch == 0 and nsteps <= state["wave_keys"].shape[0]
         for i in range(0, nsteps, per_launch):
-            launch(i, per_launch)
+            launch(i, min(per_launch, nsteps - i))
         if fold:                                                # one bucketed fold of all steps' wave keys -> keys[step]
             ops.reduce_keys(state["wave_keys"][:nsteps], state["keys"][:nsteps])
 
-    results = {}
+    results, dumped = {}, None
     for mode, per_l in (("primary", S), ("single_launch", 1)):
-        if a.no_primary or (mode == "single_launch" and (S == 1 or a.no_single)):
+        if a.no_primary or (mode == "single_launch" and (not a.full or S == 1 or a.no_single)):
             continue
-        # calibration: device time of one pass (also the untimed warm-up: W steps rounded up to whole launches)
-        lpp = max(1, math.ceil(K / per_l))
-        state["wave_keys"] = torch.zeros(max(lpp, math.ceil(W / per_l)) * per_l, per, dtype=torch.int64, device=dev)
-        state["keys"] = torch.full((state["wave_keys"].shape[0],), -1, dtype=torch.int64, device=dev)
-        run_steps(math.ceil(max(W, 1) / per_l) * per_l, per_l, fold=False)
+        plan = timed_plan(K, per_l, ring)
+        rows = plan["chunk_steps"] or plan["tail_steps"]         # steps of the longest graph = wave-key rows
+        state["wave_keys"] = torch.zeros(rows, per, dtype=torch.int64, device=dev)
+        state["keys"] = keys = torch.full((rows,), -1, dtype=torch.int64, device=dev)
+        for _ in range(math.ceil(max(W, 1) / rows)):            # untimed warm-up: at least W steps, `rows` at a time
+            run_steps(rows, per_l, fold=False)
         torch.cuda.synchronize()
-        cal = capture(torch, dev, lambda: run_steps(lpp * per_l, per_l, fold=False))
-        pass_ms = device_ms(torch, cal.replay, 3)
-        del cal
-        if world > 1:                                           # every rank must build the same plan
-            pm = torch.tensor([pass_ms], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
-            dist.all_reduce(pm, op=dist.ReduceOp.MAX)
-            pass_ms = float(pm.item())
-        # The calibration replays a ONE-pass graph, whose launch overhead a long graph does not pay per pass: plan with a margin, and if
-        # the timed region still came out under --min-ms, re-plan once from the rate it actually ran at (same launch shape either way).
-        for attempt in range(2):
-            plan = timed_plan(K, per_l, pass_ms, a.min_ms * 1.15)
-            nsteps_graph = plan["passes_per_graph"] * plan["steps_per_pass"]
-            state["wave_keys"] = torch.zeros(nsteps_graph, per, dtype=torch.int64, device=dev)
-            state["keys"] = keys = torch.full((nsteps_graph,), -1, dtype=torch.int64, device=dev)
-            body = lambda: run_steps(nsteps_graph, per_l)
-            graph = None if a.no_graph else capture(torch, dev, body)
-            if world > 1:
-                # untimed: the first collective of a given shape pays communicator / kernel set-up (ms); the timed
-                # region must only see the steady-state exchange
-                allreduce_min_keys(keys.clone())
-                dist.all_reduce(torch.zeros(1, dtype=torch.float64, device=dev), op=dist.ReduceOp.MAX)
-            warm_device(torch, graph.replay if graph is not None else body)       # untimed, beyond the W warm-up steps: steady-state clocks
-            keys.fill_(-1)
-            torch.cuda.synchronize()
-            elapsed, dev_ms = timed_region(torch, dist, world, dev, plan["replays"], graph, body, keys, allreduce_min_keys)
-            short = torch.tensor([1.0 if elapsed * 1e3 < a.min_ms else 0.0], dtype=torch.float64, device=dev if backend == "nccl" or world == 1 else "cpu")
-            if world > 1:
-                dist.all_reduce(short, op=dist.ReduceOp.MAX)                # every rank takes the same decision
-            if short.item() == 0.0:
-                break
-            pass_ms = elapsed * 1e3 / plan["repeats"]
-            del graph
-        nlaunch = plan["repeats"] * plan["launches_per_pass"]
+        runs = []
+        if plan["chunk_replays"]:
+            runs.append((lambda: run_steps(plan["chunk_steps"], per_l), plan["chunk_replays"]))
+        if plan["tail_steps"]:
+            runs.append((lambda: run_steps(plan["tail_steps"], per_l), 1))
+        if not a.no_graph:
+            runs = [(capture(torch, dev, fn).replay, n) for fn, n in runs]
+        if world > 1:
+            # untimed: the first collective of a given shape pays communicator / kernel set-up (ms); the timed
+            # region must only see the steady-state exchange
+            allreduce_min_keys(keys.clone())
+            dist.all_reduce(torch.zeros(1, dtype=torch.float64, device=dev), op=dist.ReduceOp.MAX)
+        warm_device(torch, runs[0][0], chunk=1)                 # untimed, beyond the W warm-up steps: steady-state clocks
+        keys.fill_(-1)
+        torch.cuda.synchronize()
+        elapsed, dev_ms = timed_region(torch, dist, world, dev, runs, keys, allreduce_min_keys)
         kh = keys.cpu().numpy().view(np.uint64)
-        results[mode] = dict(elapsed=elapsed, launch_ms=dev_ms / nlaunch, nlaunch=nlaunch, per=per_l, graph=graph is not None,
-                             steps_timed=plan["repeats"] * plan["steps_per_pass"], plan=plan, device_ms=dev_ms,
-                             keys_valid=bool(np.all((kh & np.uint64(0xFFFFFFFF)) < np.uint64(world * B))))
-        del graph
+        results[mode] = dict(elapsed=elapsed, launch_ms=dev_ms / plan["launches"], nlaunch=plan["launches"], per=per_l, graph=not a.no_graph,
+                             plan=plan, device_ms=dev_ms, keys_valid=bool(np.all((kh & np.uint64(0xFFFFFFFF)) < np.uint64(world * B))))
+        if mode == "primary" and a.dump_outputs and rank == 0:  # before any other leg reuses the ring
+            dumped = dump_outputs(ops, a.dump_outputs, cost[(K - 1) % ring], grad[(K - 1) % ring], keys[(K - 1) % rows:(K - 1) % rows + 1])
+        del runs
     state.pop("wave_keys", None); state.pop("keys", None)
 
-    solve_stats = None if a.no_solve else solve_leg(torch, ops, dev, B, N, rank, world)
-    voxel_stats = None if (a.no_obstacle_source or rank != 0) else obstacle_source_leg(torch, ops, dev)
+    solve_stats = None if (not a.full or a.no_solve) else solve_leg(torch, ops, dev, B, N, rank, world)
+    voxel_stats = None if (not a.full or a.no_obstacle_source or rank != 0) else obstacle_source_leg(torch, ops, dev)
     del p0, v0, goal, T, cost, grad
     torch.cuda.empty_cache()
-    config_stats = None if (a.no_configs or rank != 0) else config_legs(torch, ops, dev, a.min_ms)
-    iter_stats = None if (a.no_iterated or rank != 0) else iterated_leg(torch, ops, dev, B, N, a.min_ms, tuple(int(k) for k in a.iterated_ks.split(",")))
-    loop_stats = None if (a.no_closed_loop or rank != 0) else closed_loop_leg(torch, ops, dev)
+    config_stats = None if (not a.full or a.no_configs or rank != 0) else config_legs(torch, ops, dev, a.min_ms)
+    iter_stats = None if (not a.full or a.no_iterated or rank != 0) else iterated_leg(torch, ops, dev, B, N, a.min_ms, tuple(int(k) for k in a.iterated_ks.split(",")))
+    loop_stats = None if (not a.full or a.no_closed_loop or rank != 0) else closed_loop_leg(torch, ops, dev)
 
     if rank == 0 and a.no_primary:
         print(json.dumps({"profiling_only": True, "iterated": iter_stats, "configs": config_stats, "closed_loop": loop_stats, "solve": solve_stats}), flush=True)
     elif rank == 0:
         r = results["primary"]
         per_launch_rollouts = B * S
-        achieved = bytes_per_rollout * per_launch_rollouts / (r["launch_ms"] * 1e-3) / 1e9
+        achieved = bytes_per_rollout * B * K / (r["device_ms"] * 1e-3) / 1e9
         traffic = profiled_traffic(B, N)
-        value = world * B * r["steps_timed"] / r["elapsed"]
+        value = world * B * K / r["elapsed"]
         res = {
             "metric": "SE(3) rollouts/sec (N=30, batch=8192) + p95 solve ms, at 1/2/4/8 MI355X",
             "value": value, "unit": "rollouts/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": r["elapsed"] / r["steps_timed"] * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "ms_per_step": r["elapsed"] / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
-            "steps_timed": r["steps_timed"], "repeats": r["plan"]["repeats"], "timed_region_s": r["elapsed"],
+            "steps_timed": K, "plan": r["plan"], "timed_region_s": r["elapsed"], "full": a.full,
             "ranks_joined": joined, "dist_backend": (backend if world > 1 else None),
             "config": {"workload": f"horizon={N} SE(3) rollout + cost + thrust-gradient (+ fused batch argmin), "
                                    f"batch={B} per GPU per step, {S} independent steps per kernel launch "
                                    f"({'one multi-batch launch = grid.y' if S > 1 else 'one launch per step'}), "
                                    f"ring of {ring} distinct batches in HBM ({ring * slot_bytes / 2 ** 20:.0f} MiB), "
-                                   f"{'hipGraph replay' if r['graph'] else 'eager launches'}; a pass = ceil(steps / {S}) full launches, "
-                                   f"repeated {r['plan']['repeats']}x so the timed region lasts >= {a.min_ms:g} ms",
+                                   f"{'hipGraph replay' if r['graph'] else 'eager launches'}; the {K} timed steps = {K // S} full launches"
+                                   f"{f' + one launch of {K % S}' if K % S else ''}",
                        "horizon": N, "batch_per_gpu": B, "global_batch": world * B, "steps_per_launch": S, "ring": ring,
                        "parallelism": f"batch-sharded x{world}, one bucketed all-reduce(MIN) of the step keys"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -483,16 +509,16 @@ def main():
                          "kernel": "se3mpc::rollout_kernel<float, 30, REG, SPLIT, GRAD>", "kernel_us": r["launch_ms"] * 1e3,
                          "launches": r["nlaunch"], "rollouts_per_launch": per_launch_rollouts,
                          "bytes_per_launch": bytes_per_rollout * per_launch_rollouts,
-                         "note": "achieved = algorithmic bytes (4*(6N+10) B/rollout x rollouts per launch) / average "
-                                 "launch duration (HIP events around the launches of the timed region on the launch stream)"},
+                         "note": "achieved = algorithmic bytes (4*(6N+10) B/rollout x rollouts of the timed steps) / device time "
+                                 "(HIP events around the launches of the timed region on the launch stream)"},
             "keys_valid": r["keys_valid"],
         }
         if "single_launch" in results:
             q = results["single_launch"]
             g1 = bytes_per_rollout * B / (q["launch_ms"] * 1e-3) / 1e9
-            res["single_launch"] = {"what": "ONE kernel launch per 8192-rollout step (sequentially dependent iterations), same pass/repeat rule",
-                                    "value": world * B * q["steps_timed"] / q["elapsed"], "ms_per_step": q["elapsed"] / q["steps_timed"] * 1e3,
-                                    "steps_timed": q["steps_timed"], "repeats": q["plan"]["repeats"],
+            res["single_launch"] = {"what": "ONE kernel launch per 8192-rollout step (sequentially dependent iterations), the same K steps",
+                                    "value": world * B * K / q["elapsed"], "ms_per_step": q["elapsed"] / K * 1e3,
+                                    "steps_timed": K, "plan": q["plan"],
                                     "kernel_us": q["launch_ms"] * 1e3, "achieved_GB_per_s": g1, "frac": g1 / HBM_PEAK_GBPS,
                                     "keys_valid": q["keys_valid"]}
         if iter_stats is not None:
@@ -505,8 +531,10 @@ def main():
             res["solve"] = solve_stats
         if voxel_stats is not None:
             res["obstacle_source"] = voxel_stats
-        if a.sweep:
+        if a.full and a.sweep:
             res["sweep"] = sweep(torch, ops, prm, dev, N)
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         if cpu_stats is not None:
             res["cpu_baseline"] = cpu_stats
             res["vs_cpu_baseline"] = value / cpu_stats["value"]

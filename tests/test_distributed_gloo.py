@@ -191,17 +191,19 @@ def test_bench_gpus_n_starts_n_ranks_by_itself():
     assert r.returncode != 0 and "must agree" in r.stderr
 
 
-def test_bench_timed_plan_shape_does_not_depend_on_steps():
-    """The timed region is built from FULL launches repeated to a minimum duration, whatever --steps says."""
+def test_bench_timed_plan_covers_exactly_the_steps():
+    """--steps K times exactly K steps: full launches of S steps plus at most one launch of K mod S, replayed from hipGraphs of at most
+    MAX_GRAPH_NODES launches whose chunk walks whole ring cycles (so a replayed chunk visits the slots K consecutive steps would)."""
     import importlib.util
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
-    for K in (1, 20, 64, 65, 20000):
-        lpp = -(-K // 64)
-        p = bench.timed_plan(K, 64, pass_ms=0.065 * lpp, min_ms=20.0)
-        assert p["launches_per_pass"] == lpp and p["steps_per_pass"] == 64 * lpp
-        assert p["repeats"] * 0.065 * lpp >= 20.0 and p["passes_per_graph"] * lpp <= bench.MAX_GRAPH_NODES
-    p = bench.timed_plan(20, 1, pass_ms=20 * 0.0045, min_ms=20.0)
-    assert p["launches_per_pass"] == 20 and p["repeats"] * 20 * 0.0045 >= 20.0
+    for S, ring in ((64, 128), (64, 192), (1, 128), (1, 2)):
+        for K in (1, 20, 63, 64, 65, 127, 128, 20000, 20480, 131071, 131072, 131073, 10 ** 6):
+            p = bench.timed_plan(K, S, ring)
+            assert p["chunk_replays"] * p["chunk_steps"] + p["tail_steps"] == K
+            assert p["launches"] == p["chunk_replays"] * p["chunk_steps"] // S + -(-p["tail_steps"] // S) == -(-K // S)
+            if p["chunk_steps"]:
+                assert p["chunk_steps"] % ring == 0 and p["chunk_steps"] // S <= bench.MAX_GRAPH_NODES and p["tail_steps"] < p["chunk_steps"]
+            assert -(-p["tail_steps"] // S) <= bench.MAX_GRAPH_NODES

@@ -17,6 +17,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 import pytest
 
@@ -26,10 +27,14 @@ pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is
 
 
 def run_in_place(files):
+    """The files run in place, unchanged.  --confcutdir / --rootdir at the reference's tests/ keep pytest below it: with an inifile of
+    /dev/null alone, pytest lists every parent directory of what it collects, and those need not be listable by the user who runs the suite."""
     env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "dart_planner_amd", "compat"), ROOT, os.path.join(ROOT, "tests", "emu")]),
                PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", "-c", "/dev/null", "--rootdir=/tmp", "-p", "ref_contract_plugin", "-p", "no:cacheprovider", "-q", "-rA"]
-                       + [os.path.join(REF, f) for f in files], cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    with tempfile.TemporaryDirectory() as cwd:
+        r = subprocess.run([sys.executable, "-m", "pytest", "-c", os.devnull, "--rootdir", REF, "--confcutdir", REF, "-p", "ref_contract_plugin",
+                            "-p", "no:cacheprovider", "-q", "-rA"] + [os.path.join(REF, f) for f in files], cwd=cwd, env=env, stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, text=True, timeout=900)
     passed = set(re.findall(r"^PASSED \S*?::(\S+)", r.stdout, re.M))
     failed = set(re.findall(r"^(?:FAILED|ERROR) \S*?::(\S+?)(?: - .*)?$", r.stdout, re.M))
     return passed, failed, r.stdout

@@ -10,8 +10,8 @@ i=0
 for C in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES" \
          "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/iter_p$i -- python3 bench.py --no-primary --no-cpu-baseline --no-solve --no-obstacle-source --no-configs --no-closed-loop --iterated-ks 16 --min-ms 1 > $OUT/iter_p$i.log 2>&1 || echo "iter pass $i failed"
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/loop_p$i -- python3 bench.py --no-primary --no-cpu-baseline --no-solve --no-obstacle-source --no-configs --no-iterated > $OUT/loop_p$i.log 2>&1 || echo "loop pass $i failed"
+  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/iter_p$i -- python3 bench.py --full --no-primary --no-cpu-baseline --no-solve --no-obstacle-source --no-configs --no-closed-loop --iterated-ks 16 --min-ms 1 > $OUT/iter_p$i.log 2>&1 || echo "iter pass $i failed"
+  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/loop_p$i -- python3 bench.py --full --no-primary --no-cpu-baseline --no-solve --no-obstacle-source --no-configs --no-iterated > $OUT/loop_p$i.log 2>&1 || echo "loop pass $i failed"
 done
 python3 - <<'P'
 import csv, glob, collections

@@ -13,7 +13,7 @@ for C in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_I
   i=$((i+1))
   rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/cfg3_p$i -- python3 tools/gpu_probe_cfg3_loop.py > $OUT/cfg3_p$i.log 2>&1 || echo "cfg3 pass $i failed"
   if [ $i -le 2 ]; then
-    rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/loop_p$i -- python3 bench.py --no-primary --no-cpu-baseline --no-solve --no-obstacle-source --no-configs --no-iterated > $OUT/loop_p$i.log 2>&1 || echo "loop pass $i failed"
+    rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/loop_p$i -- python3 bench.py --full --no-primary --no-cpu-baseline --no-solve --no-obstacle-source --no-configs --no-iterated > $OUT/loop_p$i.log 2>&1 || echo "loop pass $i failed"
   fi
 done
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg3_trace -- python3 tools/gpu_probe_cfg3_loop.py > $OUT/cfg3_trace.log 2>&1

@@ -169,6 +169,8 @@ _TYPED_API = {
     "spheres_from_grid": (False, [_P, _P, _I, C.c_double, _I, C.c_double, _P, _I, _P, _P]),
     "transpose": (False, [_I, _I, _P, _I, _P, _I, _P]),
     "population_sums": (False, [_I, _I, _I, _P, _P, _D, _P, _D, _P, _P, _P]),
+    "mppi": (True, [_I, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _P]),
+    "mppi_samples": (True, [_I, _I, _I, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _P, _P, _P]),
     "solve": (True, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "plan_host": (True, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P]),
 }

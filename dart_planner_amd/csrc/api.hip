@@ -18,6 +18,8 @@ void set_last_error(const char* what, hipError_t e) {
   std::snprintf(g_last_error, sizeof(g_last_error), "%s: %s (%d)", what, hipGetErrorString(e), (int)e);
 }
 
+void set_last_message(const char* what) { std::snprintf(g_last_error, sizeof(g_last_error), "%s", what); }
+
 int check_params_impl(const se3mpc_params* p) {
   if (p == nullptr) return SE3MPC_ERR_NULL;
   if (p->horizon < 1 || p->horizon > SE3MPC_MAX_HORIZON) return SE3MPC_ERR_HORIZON;

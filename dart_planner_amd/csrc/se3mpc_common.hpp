@@ -75,6 +75,7 @@ __device__ __forceinline__ void row_bounds(const DevParams<R>& q, int row, R& lo
 
 // ---- host-side error plumbing -------------------------------------------------------------
 void set_last_error(const char* what, hipError_t e);
+void set_last_message(const char* what);   // an argument error (no HIP call involved)
 int check_params_impl(const se3mpc_params* p);
 
 inline int launch_status(const char* what) {

@@ -423,6 +423,61 @@ class Ops:
                       float(temperature), self.be.ptr(out), self.be.ptr(work), self.be.stream())
         return out
 
+    def _mppi_operands(self, params: Params, U, p0=None, v0=None, goal=None):
+        N = params.horizon
+        self._lane(U, 3 * N, "U")
+        if p0 is not None:
+            self._lane(p0, 3, "p0"); self._lane(v0, 3, "v0")
+            if params.has_goal:
+                self._lane(goal, 3, "goal")
+        return self._same(U, p0, v0, goal if params.has_goal else None), U.shape[1]
+
+    def mppi(self, params: Params, p0, v0, goal, U, n_samples: int, iters: int, sigma: float, temperature: float, seed: int = 0,
+             iter_base: int = 0, index_base: int = 0, spheres=None, obstacle_weight: float = 0.0, U_out=None, want_trace: bool = True,
+             want_keys: bool = True, iter_offset=None, B: Optional[int] = None, out=None):
+        """`iters` MPPI iterations of every problem in ONE launch (``se3mpc_mppi_*``, one workgroup per problem): perturb the nominal U
+        (3N, ld) with Philox normals of std `sigma`, roll the `n_samples` samples out, weight by exp(-(cost - min) / temperature) and move U
+        to the weighted mean.  p0, v0, goal: (3, ld); spheres: (K, 4) rows (cx, cy, cz, r), same dtype, shared by all problems.
+        -> dict(U (3N, ld), cost (ld,) with the penalty at U, trace (iters, ld) | None = the minimum sample cost per iteration,
+        keys int64 (ld,) | None = the argmin key of each problem's cost).  U_out may be U (in place); iter_offset: int32 (1,) device
+        word added to iter_base (graph replays); ``out`` = (U_out, cost, trace, keys) reuses preallocated outputs."""
+        suf, ld = self._mppi_operands(params, U, p0, v0, goal)
+        N = params.horizon
+        K = 0
+        if spheres is not None:
+            self.be.check(spheres, "spheres")
+            if spheres.ndim != 2 or spheres.shape[1] != 4 or spheres.shape[0] > SE3MPC_MAX_SPHERES or self.be.suffix(spheres) != suf:
+                raise ValueError(f"spheres: expected (K<={SE3MPC_MAX_SPHERES}, 4) {suf}, got {tuple(spheres.shape)}")
+            K = spheres.shape[0]
+        if out is not None:
+            U_out, cost, trace, keys = out
+        else:
+            U_out = U_out if U_out is not None else self.be.empty((3 * N, ld), suf)
+            cost = self.be.empty((ld,), suf)
+            trace = self.be.empty((max(int(iters), 1), ld), suf) if want_trace else None
+            keys = self.be.empty((ld,), "i64") if want_keys else None
+        self.lib.call("mppi", suf, self._B(ld, B), ld, int(n_samples), int(iters), float(sigma), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                      int(iter_base) & 0xFFFFFFFF, self.be.ptr(iter_offset), int(index_base) & 0xFFFFFFFF, self.be.ptr(p0), self.be.ptr(v0),
+                      self.be.ptr(goal if params.has_goal else None), self.be.ptr(U), self.be.ptr(U_out), self.be.ptr(spheres if K else None), K,
+                      float(obstacle_weight), self.be.ptr(cost), self.be.ptr(trace), self.be.ptr(keys), self.be.stream(), params=params)
+        return dict(U=U_out, cost=cost, trace=trace if (trace is None or iters > 0) else trace[:0], keys=keys)
+
+    def mppi_samples(self, params: Params, U, n_samples: int, sigma: float, seed: int = 0, iter_base: int = 0, index_base: int = 0,
+                     want_noise: bool = False, want_raw: bool = False, B: Optional[int] = None):
+        """The samples of ONE MPPI iteration (g = iter_base) materialised (``se3mpc_mppi_samples_*``): U (3N, ld) ->
+        dict(T (3N, S * nprob): column p * S + s = sample s of problem p, noise (3N, S * nprob) | None = its normals,
+        raw int32 (4N, S * nprob) | None = its Philox words (read them as uint32))."""
+        suf, ld = self._mppi_operands(params, U)
+        N, nB, S = params.horizon, self._B(ld, B), int(n_samples)
+        cols = max(S * nB, 1)
+        T = self.be.empty((3 * N, cols), suf)
+        noise = self.be.empty((3 * N, cols), suf) if want_noise else None
+        raw = self.be.empty((4 * N, cols), "i32") if want_raw else None
+        self.lib.call("mppi_samples", suf, nB, ld, S, float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, int(iter_base) & 0xFFFFFFFF,
+                      int(index_base) & 0xFFFFFFFF, self.be.ptr(U), self.be.ptr(T), cols, self.be.ptr(noise), self.be.ptr(raw), self.be.stream(),
+                      params=params)
+        return dict(T=T, noise=noise, raw=raw)
+
     def spheres_from_grid(self, positions, occupancy, threshold: float = 0.6, target: int = 20, radius: float = 1.0,
                           cap: int = 64):
         """Occupancy grid -> sphere table on the device (f-2).  positions (M, 3), occupancy (M,) in the

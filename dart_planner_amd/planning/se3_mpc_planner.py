@@ -498,6 +498,170 @@ class SE3MPCPlanner(BasePlanner):
                "body_rates": blk(5), "thrusts": r[18 * N:19 * N].copy()}
         return self._create_trajectory_from_solution(sol, time.time())
 
+    # ------------------------------------------------------------------ MPPI (the build's sampling planner)
+    # Defaults from the (sigma, temperature, iters) sweep of DESIGN.md 5.8 (profiles/mppi_tuning.json, tools/gpu_probe_mppi.py, 1024 samples):
+    # on the obstacle scene (10 Hz, N = 30) sigma = 4 N, temperature = 100 reaches the lowest cost of the 8-iteration grid (ends 0.8 m from the
+    # goal, safe); sigma = 1 N barely leaves hover in 8 iterations and temperature = 10^4 averages the samples flat.  On the cfg-2 distribution
+    # (dt = 0.1) sigma = 4 N is again best and temperatures 10 .. 1000 agree within 0.3 %.  8 iterations: 1.2 ms per plan (16 halve the
+    # distance left to the goal for twice the time).
+    MPPI_SAMPLES = 1024
+    MPPI_ITERS = 8
+    MPPI_SIGMA = 4.0
+    MPPI_TEMPERATURE = 100.0
+
+    def _mppi_nominal(self, N: int, warm_start: bool):
+        """The nominal thrust sequence (N, 3) this cycle starts from and the shift applied: the last cycle's nominal shifted like the warm start
+        (oracle.warm_start / _create_warm_start: drop step 0, append hover) when it exists for this horizon and goal, else hover."""
+        st = getattr(self, "_mppi_state", None)
+        hover = np.tile([0.0, 0.0, self.hover_thrust], (N, 1))
+        if not warm_start or st is None or st["U"].shape[0] != N or not np.array_equal(st["goal"], self.goal_position):
+            return hover, 0
+        U = np.empty((N, 3))
+        U[:N - 1] = st["U"][1:]
+        U[N - 1] = hover[0]
+        return U, 1
+
+    def plan_mppi(self, current_state: DroneState, goal_position, n_samples: int = MPPI_SAMPLES, iters: int = MPPI_ITERS,
+                  sigma: float = MPPI_SIGMA, temperature: float = MPPI_TEMPERATURE, seed: int = 0, precision: str = "f32", obstacles=None,
+                  obstacle_weight: Optional[float] = None, warm_start: bool = True) -> Trajectory:
+        """MPPI, the sampling counterpart of :meth:`plan_shooting` (the build's construct): `iters` iterations of perturb-the-nominal (Philox
+        normals of std `sigma` newtons) / roll out `n_samples` samples / weight by exp(-(cost - min) / temperature) / move the nominal to the
+        weighted mean, in ONE launch of ``se3mpc_mppi_*``; the nominal is then rolled out in float64 with states and extracted
+        (``se3mpc_shooting_finish_*`` through the kernel's argmin key).  The nominal is kept between calls: with ``warm_start`` the next
+        plan starts from it shifted by one step (hover appended), a goal change through ``sense`` resets it to hover, and every call draws
+        fresh noise (the iteration counter advances).  obstacles / obstacle_weight as :meth:`plan_shooting`.  ``last_result``: cost (the
+        running cost at the plan), penalty, cost_with_penalty, trace (the minimum sample cost per iteration), shift (1 = warm-started),
+        iter_base, n_samples, iters.  With a graph-capable backend the whole plan is one hipGraph replay."""
+        current_state, _, _ = self.sense(current_state, goal_position)
+        ops = self._get_ops()
+        prm = self._params()
+        N = self.se3_config.prediction_horizon
+        p0 = np.asarray(to_float(current_state.position), float)
+        v0 = np.asarray(to_float(current_state.velocity), float)
+        sph = self._obstacle_table(obstacles)
+        w_obs = float(self.se3_config.obstacle_weight if obstacle_weight is None else obstacle_weight)
+        U0, shift = self._mppi_nominal(N, warm_start)
+        it_base = getattr(self, "_mppi_iter_base", 0)
+        args = (ops, prm, p0, v0, U0, int(n_samples), int(iters), float(sigma), float(temperature), int(seed), precision, sph, w_obs, it_base)
+        if getattr(ops.be, "graph_capable", False):
+            r, trace = self._plan_mppi_captured(*args)
+        else:
+            r, trace = self._plan_mppi_eager(*args)
+        self._mppi_iter_base = (it_base + int(iters)) & 0xFFFFFFFF
+        blk = lambda i: r[3 * N * i:3 * N * (i + 1)].reshape(N, 3).copy()
+        self._mppi_state = dict(U=blk(2), goal=np.array(self.goal_position, dtype=float))
+        self.last_result = dict(cost=float(r[19 * N]), penalty=float(r[19 * N + 1]), cost_with_penalty=float(r[19 * N + 2]), trace=trace,
+                                shift=shift, iter_base=it_base, n_samples=int(n_samples), iters=int(iters), U=blk(2))
+        sol = {"positions": blk(0), "velocities": blk(1), "thrust_vectors": blk(2), "accelerations": blk(3), "attitudes": blk(4),
+               "body_rates": blk(5), "thrusts": r[18 * N:19 * N].copy()}
+        return self._create_trajectory_from_solution(sol, time.time())
+
+    def _plan_mppi_eager(self, ops, prm, p0, v0, U0, n_samples, iters, sigma, temperature, seed, precision, sph, w_obs, it_base):
+        """plan_mppi launch by launch (any backend): -> (packed float64 result of se3mpc_shooting_finish_*, trace)."""
+        N = prm.horizon
+        be = ops.be
+        suf = "f32" if precision == "f32" else "f64"
+        col = lambda a, kind: be.from_host(np.ascontiguousarray(np.asarray(a, float).reshape(-1, 1).astype(np.float32 if kind == "f32" else np.float64)))
+        state = be.from_host(np.concatenate([p0, v0, self.goal_position]).astype(np.float64))
+        sph_r = None if sph is None else be.from_host(np.ascontiguousarray(sph.astype(np.float32 if suf == "f32" else np.float64)))
+        out = ops.mppi(prm, col(p0, suf), col(v0, suf), col(self.goal_position, suf), col(U0, suf), n_samples, iters, sigma, temperature, seed=seed,
+                       iter_base=it_base, spheres=sph_r, obstacle_weight=w_obs)
+        res = be.empty((19 * N + 3,), "f64")
+        sph_d = None if sph is None else be.from_host(np.ascontiguousarray(sph.astype(np.float64)))
+        ops.shooting_finish(prm, out["U"], out["keys"], state, res, spheres=sph_d, obstacle_weight=w_obs)
+        return np.asarray(be.to_host(res), dtype=float).copy(), np.asarray(be.to_host(out["trace"]), dtype=float)[:, 0].copy()
+
+    def _plan_mppi_captured(self, ops, prm, p0, v0, U0, n_samples, iters, sigma, temperature, seed, precision, sph, w_obs, it_base):
+        """plan_mppi as ONE hipGraph replay: state, nominal and iteration counter in through pinned buffers -> ``se3mpc_mppi_*`` (the counter read
+        from a device word, so one capture serves every cycle) -> ``se3mpc_shooting_finish_*`` on its key -> packed result and trace out through
+        pinned buffers; the host synchronises once.  Same numbers as :meth:`_plan_mppi_eager`."""
+        import torch
+        N = prm.horizon
+        K = 0 if sph is None else len(sph)
+        key = (N, n_samples, iters, sigma, temperature, seed, precision, bytes(prm), K, w_obs)
+        graphs = self.__dict__.setdefault("_mppi_graphs", {})
+        g = graphs.get(key)
+        if g is None:
+            dev = ops.be.device
+            dt = torch.float32 if precision == "f32" else torch.float64
+            pin = lambda n, t=torch.float64: torch.zeros(n, dtype=t).pin_memory()
+            io = dict(h_in=pin(9 + 3 * N), d_in=torch.zeros(9 + 3 * N, dtype=torch.float64, device=dev), h_it=pin(1, torch.int32),
+                      d_it=torch.zeros(1, dtype=torch.int32, device=dev), h_out=pin(19 * N + 3), h_trace=pin(max(iters, 1), dt),
+                      d_U=torch.empty((3 * N, 1), dtype=dt, device=dev), d_cost=torch.empty(1, dtype=dt, device=dev),
+                      d_trace=torch.empty((max(iters, 1), 1), dtype=dt, device=dev), d_keys=torch.empty(1, dtype=torch.int64, device=dev),
+                      d_s=torch.empty((3, 3, 1), dtype=dt, device=dev), d_U0=torch.empty((3 * N, 1), dtype=dt, device=dev))
+            if K:
+                io.update(h_sph=pin((K, 4)), d_sph=torch.zeros((K, 4), dtype=torch.float64, device=dev), d_sph_r=torch.empty((K, 4), dtype=dt, device=dev))
+            io["h_in_np"], io["h_it_np"], io["h_out_np"], io["h_trace_np"] = (io[k].numpy() for k in ("h_in", "h_it", "h_out", "h_trace"))
+            if K:
+                io["h_sph_np"] = io["h_sph"].numpy()
+
+            def body():
+                io["d_in"].copy_(io["h_in"], non_blocking=True)
+                io["d_it"].copy_(io["h_it"], non_blocking=True)
+                io["d_s"].copy_(io["d_in"][:9].view(3, 3, 1))                 # (p0, v0, goal) in the kernel's type
+                io["d_U0"].copy_(io["d_in"][9:].view(3 * N, 1))
+                if K:
+                    io["d_sph"].copy_(io["h_sph"], non_blocking=True)
+                    io["d_sph_r"].copy_(io["d_sph"])
+                ops.mppi(prm, io["d_s"][0], io["d_s"][1], io["d_s"][2], io["d_U0"], n_samples, iters, sigma, temperature, seed=seed, iter_base=0,
+                         iter_offset=io["d_it"], spheres=io["d_sph_r"] if K else None, obstacle_weight=w_obs,
+                         out=(io["d_U"], io["d_cost"], io["d_trace"], io["d_keys"]))
+                ops.shooting_finish(prm, io["d_U"], io["d_keys"], io["d_in"], io["h_out"], spheres=io["d_sph"] if K else None, obstacle_weight=w_obs)
+                io["h_trace"].copy_(io["d_trace"].view(-1), non_blocking=True)
+
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                body()                                                             # warm-up outside the capture
+            torch.cuda.current_stream(dev).wait_stream(side)
+            torch.cuda.synchronize(dev)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                body()
+            if len(graphs) >= 4:
+                graphs.pop(next(iter(graphs)))
+            g = graphs[key] = (graph, io)
+        graph, io = g
+        hin = io["h_in_np"]
+        hin[0:3] = p0; hin[3:6] = v0; hin[6:9] = self.goal_position; hin[9:] = U0.reshape(-1)
+        io["h_it_np"][0] = np.array(it_base, dtype=np.uint32).view(np.int32)        # the kernel reads the word as uint32
+        if K:
+            io["h_sph_np"][...] = sph
+        graph.replay()
+        torch.cuda.current_stream(ops.be.device).synchronize()
+        return io["h_out_np"].copy(), io["h_trace_np"][:iters].astype(float)
+
+    def plan_batch_mppi(self, positions, velocities, goals, n_samples: int = MPPI_SAMPLES, iters: int = MPPI_ITERS, sigma: float = MPPI_SIGMA,
+                        temperature: float = MPPI_TEMPERATURE, seed: int = 0, precision: Optional[str] = None, obstacles=None,
+                        obstacle_weight: Optional[float] = None, nominal=None, iter_base: int = 0) -> Dict[str, np.ndarray]:
+        """MPPI for B independent (state, goal) problems in ONE launch (problem b draws the noise of index b): positions, velocities, goals (B, 3);
+        nominal (B, N, 3) or None = hover.  Returns arrays with a leading B axis: positions, velocities, thrust_vectors, accelerations,
+        attitudes, body_rates (B, N, 3), thrusts (B, N), cost (B,) with the penalty, trace (B, iters)."""
+        p0 = np.asarray(to_float(positions), float).reshape(-1, 3)
+        v0 = np.asarray(to_float(velocities), float).reshape(-1, 3)
+        g = np.asarray(to_float(goals), float).reshape(-1, 3)
+        if not (p0.shape == v0.shape == g.shape):
+            raise ValueError("positions, velocities and goals must all be (B, 3)")
+        B, N = len(p0), self.se3_config.prediction_horizon
+        U = np.tile([0.0, 0.0, self.hover_thrust], (B, N, 1)) if nominal is None else np.asarray(nominal, float).reshape(B, N, 3)
+        ops = self._get_ops()
+        be = ops.be
+        prm = self._params(has_goal=1)
+        npdt = np.float32 if (precision or "f32") == "f32" else np.float64
+        lane = lambda a: be.from_host(np.ascontiguousarray(np.asarray(a, float).reshape(B, -1).T.astype(npdt)))
+        sph = self._obstacle_table(obstacles)
+        w_obs = float(self.se3_config.obstacle_weight if obstacle_weight is None else obstacle_weight)
+        lp0, lv0, lg = lane(p0), lane(v0), lane(g)
+        out = ops.mppi(prm, lp0, lv0, lg, lane(U), n_samples, iters, sigma, temperature, seed=seed, iter_base=iter_base,
+                       spheres=None if sph is None else be.from_host(np.ascontiguousarray(sph.astype(npdt))), obstacle_weight=w_obs, want_keys=False)
+        _, _, P, V = ops.rollout_cost_grad(prm, lp0, lv0, lg, out["U"], want_grad=False, want_states=True)
+        acc, att, rates, thr = ops.extract(prm, out["U"])
+        h = lambda a, shape: np.asarray(be.to_host(a), dtype=float).T.reshape(shape).copy()
+        return dict(positions=h(P, (B, N, 3)), velocities=h(V, (B, N, 3)), thrust_vectors=h(out["U"], (B, N, 3)), accelerations=h(acc, (B, N, 3)),
+                    attitudes=h(att, (B, N, 3)), body_rates=h(rates, (B, N, 3)), thrusts=h(thr, (B, N)), cost=h(out["cost"], (B,)),
+                    trace=h(out["trace"], (B, iters)) if iters > 0 else np.zeros((B, 0)))
+
     def _create_warm_start(self, current_state: DroneState, N: int) -> np.ndarray:
         """planner.py:294-327: shift the previous solution by one step, re-anchor step 0 at the current
         state, extend to the goal with hover thrust."""

@@ -316,6 +316,39 @@ int se3mpc_population_sums_f32(int rows, int B, int ld, const float* X, const fl
 int se3mpc_population_sums_f64(int rows, int B, int ld, const double* X, const double* cost, double cost_ref,
                                const uint64_t* ref_key, double temperature, double* out, double* workspace, void* stream);
 
+/* MPPI (model-predictive path integral) on the shooting form, `iters` iterations of `nprob` independent problems in ONE launch (one
+ * workgroup per problem; nothing per sample touches HBM).  Lane layout over problems: p0, v0, goal: [3][ld]; U_in, U_out: [3N][ld] (the
+ * nominal thrust sequence, rows 3k+a as the T block; U_out may alias U_in); cost: [ld]; trace: NULL or [iters][ld]; keys: NULL or [ld].
+ * Iteration i (g = iter_base + *iter_offset + i; iter_offset: NULL or a device word, so that a captured graph can advance it) of problem
+ * q = index_base + p:
+ *   noise   x0..x3 = Philox4x32-10(counter (q, s, g, k), key (seed & 0xffffffff, seed >> 32)), u_j = (x_j + 0.5) * 2^-32 in the entry
+ *           point's type, n = (sqrt(-2 ln u0) cos 2 pi u1, sqrt(-2 ln u0) sin 2 pi u1, sqrt(-2 ln u2) cos 2 pi u3); sample s = 0 has none
+ *   sample  T_s[k][a] = clip(U[k][a] + sigma * n_a) into the thrust box of se3mpc_projected_step_* (+-txy for x, y; [min, max] for z)
+ *   cost    c_s = the cost of se3mpc_rollout_cost_grad_* at T_s + obstacle_weight * sum_k sum_j max(0, -(|P_k - c_j|^2 - (r_j + margin)^2))^2
+ *           (the penalty of se3mpc_rollout_iterate_obstacles_*; spheres: [K][4] rows (cx, cy, cz, r) shared by all problems, K = 0: none)
+ *   update  m = min_s c_s, w_s = exp(-(c_s - m) / temperature), U <- sum_s w_s T_s / sum_s w_s, accumulated in float64 in a fixed order
+ *           (results are identical run to run); trace[i][p] = m.
+ * cost[p] = the cost (with the penalty) of U_out, evaluated once after the last update; keys[p] = orderable(cost) << 32 | q, the key of
+ * se3mpc_argmin_* (se3mpc_shooting_finish_*(B = 1, n_slots = 1) takes it as is).  iters = 0 evaluates and copies U_in.  nprob = 0 is a
+ * no-op.  64 <= S <= 65536, S a multiple of 64 (SE3MPC_ERR_SHAPE otherwise, as K outside [0, SE3MPC_MAX_SPHERES]); sigma >= 0, temperature
+ * > 0 and obstacle_weight >= 0 finite (SE3MPC_ERR_PARAM).  Every rejected call sets se3mpc_last_error and launches nothing.
+ * temperature is absolute, in cost units. */
+int se3mpc_mppi_f32(const se3mpc_params* p, int nprob, int ld, int S, int iters, double sigma, double temperature, uint64_t seed,
+                    uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const float* p0, const float* v0, const float* goal,
+                    const float* U_in, float* U_out, const float* spheres, int K, double obstacle_weight, float* cost, float* trace,
+                    uint64_t* keys, void* stream);
+int se3mpc_mppi_f64(const se3mpc_params* p, int nprob, int ld, int S, int iters, double sigma, double temperature, uint64_t seed,
+                    uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const double* p0, const double* v0, const double* goal,
+                    const double* U_in, double* U_out, const double* spheres, int K, double obstacle_weight, double* cost, double* trace,
+                    uint64_t* keys, void* stream);
+/* The samples of ONE iteration (g = iter_base) of se3mpc_mppi_*, materialised for inspection: column p * S + s of T_out [3N][ld_out]
+ * (ld_out >= S * nprob) is T_s of problem p; noise: NULL or [3N][ld_out] = the normals n of that column (drawn for s = 0 too, where the
+ * sample does not use them); raw: NULL or [4N][ld_out] = the Philox words, row 4k + j = x_j of step k.  Same argument rules. */
+int se3mpc_mppi_samples_f32(const se3mpc_params* p, int nprob, int ld, int S, double sigma, uint64_t seed, uint32_t iter_base,
+                            uint32_t index_base, const float* U_in, float* T_out, int ld_out, float* noise, uint32_t* raw, void* stream);
+int se3mpc_mppi_samples_f64(const se3mpc_params* p, int nprob, int ld, int S, double sigma, uint64_t seed, uint32_t iter_base,
+                            uint32_t index_base, const double* U_in, double* T_out, int ld_out, double* noise, uint32_t* raw, void* stream);
+
 /* Obstacle source: the sphere table of se3mpc_obstacle_residual_* straight from a local
  * occupancy grid, replacing the host loop of cloud/main_improved_threelayer.py:387-398 (target 20) and
  * tests/test_se3_mpc_with_mapper.py:29-33 (target 10): occupied = cells with occupancy > threshold in grid

@@ -170,6 +170,8 @@ _TYPED_API = {
     "transpose": (False, [_I, _I, _P, _I, _P, _I, _P]),
     "population_sums": (False, [_I, _I, _I, _P, _P, _D, _P, _D, _P, _P, _P]),
     "mppi": (True, [_I, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _P]),
+    "mppi_split": (True, [_I, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _I, _P, C.c_size_t,
+                          _P]),
     "mppi_samples": (True, [_I, _I, _I, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _P, _P, _P]),
     "solve": (True, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "plan_host": (True, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_double, _P]),
@@ -220,6 +222,7 @@ _PLAIN_API = {
     "se3mpc_key_index": (C.c_uint32, [C.c_uint64]),
     "se3mpc_key_cost": (C.c_float, [C.c_uint64]),
     "se3mpc_population_workspace": (C.c_int, [_I, _I]),
+    "se3mpc_mppi_split_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
 }
 
 
@@ -306,6 +309,9 @@ class Library:
 
     def population_workspace(self, rows: int, B: int) -> int:
         return self._dll.se3mpc_population_workspace(rows, B)
+
+    def mppi_split_workspace_bytes(self, horizon: int, nprob: int, splits: int) -> int:
+        return self._dll.se3mpc_mppi_split_workspace_bytes(horizon, nprob, splits)
 
     def key_index(self, key: int) -> int:
         return self._dll.se3mpc_key_index(C.c_uint64(key))

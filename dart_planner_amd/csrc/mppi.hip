@@ -12,182 +12,10 @@
 // The weighted sum needs T_s after the chunk's minimum is known: it is regenerated from the counter (a second Philox + Box-Muller per
 // step, no rollout) rather than held in 3N registers -- held, the kernel spills at every horizon where it would pay.
 // Chunks fold into the running sums with a streaming rescale exp(-(m_new - m_old) / lambda), so S is not bounded by LDS.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-
-#include "se3mpc_common.hpp"
-#include "closed_loop_device.hpp"
-#include <se3mpc_wave_ops.hpp>
+#include "mppi_device.hpp"
 
 namespace se3mpc {
 namespace mppi {
-
-constexpr int kBlock = 256;                // workgroup width (samples per pass); S < 256 runs S lanes
-constexpr int kMinS = 64, kMaxS = 65536;
-constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
-constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
-
-// Philox4x32-10 (Salmon et al., SC'11): ten rounds, the key bumped between rounds.  The 32 x 32 -> 64 products are plain uint64_t
-// arithmetic (v_mul_lo_u32 / v_mul_hi_u32); the first round's products of the uniform counter words q and g go to the scalar unit.
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r) { k0 += kPhiloxW0; k1 += kPhiloxW1; }
-    const uint64_t a = (uint64_t)kPhiloxM0 * c[0], b = (uint64_t)kPhiloxM1 * c[2];
-    const uint32_t n0 = (uint32_t)(b >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(a >> 32) ^ c[3] ^ k1;
-    c[0] = n0; c[1] = (uint32_t)b; c[2] = n2; c[3] = (uint32_t)a;
-  }
-}
-
-// Box-Muller on the four words of one Philox block: three standard normals
-template <typename R>
-__device__ __forceinline__ void box_muller(const uint32_t x[4], R n[3]) {
-  const R scale = (R)2.3283064365386962890625e-10;          // 2^-32
-  const R two_pi = (R)6.283185307179586476925;
-  const R u0 = ((R)x[0] + (R)0.5) * scale, u1 = ((R)x[1] + (R)0.5) * scale;
-  const R u2 = ((R)x[2] + (R)0.5) * scale, u3 = ((R)x[3] + (R)0.5) * scale;
-  const R r01 = sqrt((R)-2 * log(u0)), r23 = sqrt((R)-2 * log(u2));
-  R s1, c1;
-  sin_cos(two_pi * u1, s1, c1);
-  n[0] = r01 * c1;
-  n[1] = r01 * s1;
-  n[2] = r23 * cos(two_pi * u3);
-}
-
-template <typename R>
-__device__ __forceinline__ R box_clip(const DevParams<R>& q, int a, R t) {
-  const R lo = (a == 2) ? q.tz_lo : -q.txy, hi = (a == 2) ? q.tz_hi : q.txy;
-  return fmin(fmax(t, lo), hi);
-}
-
-__device__ __forceinline__ uint32_t orderable_cost_bits(float c) {        // the key order of se3mpc_argmin_*
-  const uint32_t u = __float_as_uint(c);
-  if (c != c) return 0xFFFFFFFEu;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-template <typename R>
-struct Ctx {
-  DevParams<R> q;
-  uint32_t key0, key1, qi, g;
-  const R* U;       // LDS [3N]
-  const R* sph;     // LDS [K][4] = (cx, cy, cz, (r + margin)^2)
-  int K;
-  R w_obs;
-  R p0[3], v0[3], gl[3];
-};
-
-// Sample s at step k: the noise (raw words / normals optional) and the clipped thrust.  The one expression mppi_samples_kernel and
-// the fused kernel share, so the two agree bit for bit.
-template <typename R>
-__device__ __forceinline__ void draw(const Ctx<R>& c, const R* Uk, uint32_t s, int k, R sig, R t[3], uint32_t* raw = nullptr, R* nrm = nullptr) {
-  uint32_t x[4] = {c.qi, s, c.g, (uint32_t)k};
-  philox4x32_10(x, c.key0, c.key1);
-  R n[3];
-  box_muller<R>(x, n);
-  if (raw != nullptr) { raw[0] = x[0]; raw[1] = x[1]; raw[2] = x[2]; raw[3] = x[3]; }
-  if (nrm != nullptr) { nrm[0] = n[0]; nrm[1] = n[1]; nrm[2] = n[2]; }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) t[a] = box_clip(c.q, a, Uk[a] + sig * n[a]);
-}
-
-template <typename R>
-struct Roll {
-  R p[3], v[3];
-  R sp, sterm, sv, sa, st, pen;
-};
-
-// One step of the forward sweep (planner.py:449-460 solved forward, the objective of :516-550, the sphere penalty on P_k)
-template <typename R>
-__device__ __forceinline__ void roll_step(const Ctx<R>& c, Roll<R>& r, int k, const R t[3]) {
-  const DevParams<R>& q = c.q;
-  R acc[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    acc[a] = t[a] * q.inv_mass - ((a == 2) ? q.grav : (R)0);
-    const R dev = t[a] - ((a == 2) ? q.hover : (R)0);
-    const R e = r.p[a] - c.gl[a];
-    if (k == q.N - 1) r.sterm += e * e; else r.sp += e * e;
-    r.sv += r.v[a] * r.v[a];
-    r.sa += acc[a] * acc[a];
-    r.st += dev * dev;
-  }
-  for (int j = 0; j < c.K; ++j) {
-    const R* s4 = c.sph + 4 * j;
-    const R dx = r.p[0] - s4[0], dy = r.p[1] - s4[1], dz = r.p[2] - s4[2];
-    const R cc = dz * dz + (dy * dy + (dx * dx - s4[3]));
-    const R h = fmax((R)0, -cc);
-    r.pen += h * h;
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    r.p[a] = r.p[a] + r.v[a] * q.dt + q.half_dt2 * acc[a];
-    r.v[a] = r.v[a] + acc[a] * q.dt;
-  }
-}
-
-template <typename R>
-__device__ __forceinline__ Roll<R> roll_begin(const Ctx<R>& c) {
-  Roll<R> r;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) { r.p[a] = c.p0[a]; r.v[a] = c.v0[a]; }
-  r.sp = r.sterm = r.sv = r.sa = r.st = r.pen = (R)0;
-  return r;
-}
-
-template <typename R>
-__device__ __forceinline__ R roll_total(const Ctx<R>& c, const Roll<R>& r) {
-  const DevParams<R>& q = c.q;
-  R cost = q.wv * r.sv + q.wa * r.sa + q.wT * r.st;
-  if (q.has_goal) cost += q.wp * (r.sp + r.sterm) + q.term * q.wp * r.sterm;
-  return cost + c.w_obs * r.pen;
-}
-
-// Cost of sample s (NOISE) or of the nominal as it stands (!NOISE: no draw, no clip -- the final evaluation)
-template <typename R, bool NOISE>
-__device__ __forceinline__ R sample_cost(const Ctx<R>& c, uint32_t s, R sig) {
-  Roll<R> r = roll_begin(c);
-  for (int k = 0; k < c.q.N; ++k) {
-    R t[3];
-    if (NOISE) draw(c, c.U + 3 * k, s, k, sig, t); else { t[0] = c.U[3 * k]; t[1] = c.U[3 * k + 1]; t[2] = c.U[3 * k + 2]; }
-    roll_step(c, r, k, t);
-  }
-  return roll_total(c, r);
-}
-
-// LDS carve-up of the fused kernel (bytes, every region 16-byte aligned): acc [3N + 1] double | part [W][3N + 1] double | red [W] double |
-// U [3N] R | sph [K][4] R
-struct Lds {
-  size_t acc, part, red, U, sph, total;
-};
-__host__ __device__ inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-__host__ __device__ inline Lds lds_layout(int N, int K, int W, size_t esz) {
-  Lds l;
-  const size_t rows1 = (size_t)3 * N + 1;
-  l.acc = 0;
-  l.part = align16(l.acc + rows1 * 8);
-  l.red = align16(l.part + (size_t)W * rows1 * 8);
-  l.U = align16(l.red + (size_t)W * 8);
-  l.sph = align16(l.U + (size_t)3 * N * esz);
-  l.total = align16(l.sph + (size_t)4 * K * esz);
-  return l;
-}
-
-template <typename R>
-__device__ __forceinline__ Ctx<R> load_ctx(const DevParams<R>& q, int ld, int p, uint32_t key0, uint32_t key1, uint32_t qi, const R* p0,
-                                           const R* v0, const R* goal, const R* U, const R* sph, int K, R w_obs) {
-  Ctx<R> c;
-  c.q = q; c.key0 = key0; c.key1 = key1; c.qi = qi; c.g = 0; c.U = U; c.sph = sph; c.K = K; c.w_obs = w_obs;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    c.p0[a] = p0[(size_t)a * ld + p];
-    c.v0[a] = v0[(size_t)a * ld + p];
-    c.gl[a] = q.has_goal ? goal[(size_t)a * ld + p] : (R)0;
-  }
-  return c;
-}
 
 // The fused planner: one workgroup of min(S, kBlock) lanes per problem, `iters` iterations, then one evaluation of the nominal.
 template <typename R>
@@ -198,7 +26,7 @@ mppi_kernel(DevParams<R> q, int ld, int S, int iters, R sigma, double inv_lam, u
             R* __restrict__ trace, uint64_t* __restrict__ keys) {
   HIP_DYNAMIC_SHARED(unsigned char, lds_raw)
   const int N = q.N, rows = 3 * N, NT = (int)blockDim.x, W = NT / kWave;
-  const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int tid = (int)threadIdx.x, wave = tid / kWave;
   const int p = (int)blockIdx.x;
   const Lds L = lds_layout(N, K, W, sizeof(R));
   double* acc = reinterpret_cast<double*>(lds_raw + L.acc);
@@ -207,55 +35,13 @@ mppi_kernel(DevParams<R> q, int ld, int S, int iters, R sigma, double inv_lam, u
   R* U = reinterpret_cast<R*>(lds_raw + L.U);
   R* sph = reinterpret_cast<R*>(lds_raw + L.sph);
   for (int r = tid; r < rows; r += NT) U[r] = U_in[(size_t)r * ld + p];
-  for (int i = tid; i < 4 * K; i += NT) {
-    const R v = spheres[i];
-    sph[i] = ((i & 3) == 3) ? (v + q.margin) * (v + q.margin) : v;
-  }
+  stage_spheres(q, spheres, K, sph);
   Ctx<R> c = load_ctx(q, ld, p, key0, key1, index_base + (uint32_t)p, p0, v0, goal, U, sph, K, w_obs);
   const uint32_t g0 = iter_base + (iter_offset != nullptr ? *iter_offset : 0u);
-  const double kInf = __builtin_huge_val();
   __syncthreads();
   for (int it = 0; it < iters; ++it) {
     c.g = g0 + (uint32_t)it;
-    double m = kInf;
-    for (int c0 = 0; c0 < S; c0 += NT) {
-      const uint32_t s = (uint32_t)(c0 + tid);
-      const bool live = c0 + tid < S;
-      const R sig = s == 0 ? (R)0 : sigma;
-      double cd = kInf;
-      if (live) {
-        const R cs = sample_cost<R, true>(c, s, sig);
-        if (cs == cs) cd = (double)cs;                     // a NaN cost weighs nothing
-      }
-      // chunk minimum: wavefront min, then the W partials in wavefront order
-      const double wm = wave_min(cd);
-      if (lane == 0) red[wave] = wm;
-      __syncthreads();
-      double mc = red[0];
-      for (int w = 1; w < W; ++w) mc = fmin(mc, red[w]);
-      const double mn = fmin(m, mc);
-      const double scale = (m < kInf) ? exp((mn - m) * inv_lam) : 0.0;     // earlier chunks re-expressed against the new minimum
-      const double wgt = (cd < kInf) ? exp(-(cd - mn) * inv_lam) : 0.0;
-      double* mine = part + (size_t)wave * (rows + 1);
-      // weighted rows of this chunk (T_s regenerated): wavefront sums three rows at a time, one partial per wavefront in LDS
-      for (int k = 0; k < N; ++k) {
-        R t[3];
-        draw(c, U + 3 * k, s, k, sig, t);
-        double v3[3] = {wgt > 0.0 ? wgt * (double)t[0] : 0.0, wgt > 0.0 ? wgt * (double)t[1] : 0.0, wgt > 0.0 ? wgt * (double)t[2] : 0.0};
-        wave_sum_n<3>(v3);
-        if (lane == 0) { mine[3 * k] = v3[0]; mine[3 * k + 1] = v3[1]; mine[3 * k + 2] = v3[2]; }
-      }
-      const double ws = wave_sum(wgt);
-      if (lane == 0) mine[rows] = ws;
-      __syncthreads();
-      for (int r = tid; r <= rows; r += NT) {
-        double sum = part[r];
-        for (int w = 1; w < W; ++w) sum += part[(size_t)w * (rows + 1) + r];
-        acc[r] = (c0 == 0) ? sum : acc[r] * scale + sum;
-      }
-      m = mn;
-      __syncthreads();
-    }
+    const double m = weighted_pass<R>(c, U, 0, S, sigma, inv_lam, acc, part, red);
     // U <- weighted mean (the clip only guards the rounding of the division: a mean of in-box samples is in the box)
     const double wsum = acc[rows];
     for (int r = tid; r < rows; r += NT)
@@ -263,13 +49,7 @@ mppi_kernel(DevParams<R> q, int ld, int S, int iters, R sigma, double inv_lam, u
     if (tid == 0 && trace != nullptr) trace[(size_t)it * ld + p] = (R)m;
     __syncthreads();
   }
-  if (wave == 0) {
-    const R cf = sample_cost<R, false>(c, 0u, (R)0);
-    if (lane == 0) {
-      cost_out[p] = cf;
-      if (keys != nullptr) keys[p] = ((uint64_t)orderable_cost_bits((float)cf) << 32) | (uint64_t)(index_base + (uint32_t)p);
-    }
-  }
+  if (wave == 0) write_nominal_cost(c, p, index_base, cost_out, keys);
   for (int r = tid; r < rows; r += NT) U_out[(size_t)r * ld + p] = U[r];
 }
 

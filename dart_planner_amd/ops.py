@@ -432,15 +432,10 @@ class Ops:
                 self._lane(goal, 3, "goal")
         return self._same(U, p0, v0, goal if params.has_goal else None), U.shape[1]
 
-    def mppi(self, params: Params, p0, v0, goal, U, n_samples: int, iters: int, sigma: float, temperature: float, seed: int = 0,
-             iter_base: int = 0, index_base: int = 0, spheres=None, obstacle_weight: float = 0.0, U_out=None, want_trace: bool = True,
-             want_keys: bool = True, iter_offset=None, B: Optional[int] = None, out=None):
-        """`iters` MPPI iterations of every problem in ONE launch (``se3mpc_mppi_*``, one workgroup per problem): perturb the nominal U
-        (3N, ld) with Philox normals of std `sigma`, roll the `n_samples` samples out, weight by exp(-(cost - min) / temperature) and move U
-        to the weighted mean.  p0, v0, goal: (3, ld); spheres: (K, 4) rows (cx, cy, cz, r), same dtype, shared by all problems.
-        -> dict(U (3N, ld), cost (ld,) with the penalty at U, trace (iters, ld) | None = the minimum sample cost per iteration,
-        keys int64 (ld,) | None = the argmin key of each problem's cost).  U_out may be U (in place); iter_offset: int32 (1,) device
-        word added to iter_base (graph replays); ``out`` = (U_out, cost, trace, keys) reuses preallocated outputs."""
+    def _mppi_call(self, base, tail, params, p0, v0, goal, U, n_samples, iters, sigma, temperature, seed, iter_base, index_base, spheres,
+                   obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out):
+        """The operand checks, output allocation and call shared by :meth:`mppi` and :meth:`mppi_split`; ``tail``: the arguments between
+        ``keys`` and ``stream``."""
         suf, ld = self._mppi_operands(params, U, p0, v0, goal)
         N = params.horizon
         K = 0
@@ -456,11 +451,48 @@ class Ops:
             cost = self.be.empty((ld,), suf)
             trace = self.be.empty((max(int(iters), 1), ld), suf) if want_trace else None
             keys = self.be.empty((ld,), "i64") if want_keys else None
-        self.lib.call("mppi", suf, self._B(ld, B), ld, int(n_samples), int(iters), float(sigma), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        self.lib.call(base, suf, self._B(ld, B), ld, int(n_samples), int(iters), float(sigma), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
                       int(iter_base) & 0xFFFFFFFF, self.be.ptr(iter_offset), int(index_base) & 0xFFFFFFFF, self.be.ptr(p0), self.be.ptr(v0),
                       self.be.ptr(goal if params.has_goal else None), self.be.ptr(U), self.be.ptr(U_out), self.be.ptr(spheres if K else None), K,
-                      float(obstacle_weight), self.be.ptr(cost), self.be.ptr(trace), self.be.ptr(keys), self.be.stream(), params=params)
+                      float(obstacle_weight), self.be.ptr(cost), self.be.ptr(trace), self.be.ptr(keys), *tail, self.be.stream(),
+                      params=params)
         return dict(U=U_out, cost=cost, trace=trace if (trace is None or iters > 0) else trace[:0], keys=keys)
+
+    def mppi(self, params: Params, p0, v0, goal, U, n_samples: int, iters: int, sigma: float, temperature: float, seed: int = 0,
+             iter_base: int = 0, index_base: int = 0, spheres=None, obstacle_weight: float = 0.0, U_out=None, want_trace: bool = True,
+             want_keys: bool = True, iter_offset=None, B: Optional[int] = None, out=None):
+        """`iters` MPPI iterations of every problem in ONE launch (``se3mpc_mppi_*``, one workgroup per problem): perturb the nominal U
+        (3N, ld) with Philox normals of std `sigma`, roll the `n_samples` samples out, weight by exp(-(cost - min) / temperature) and move U
+        to the weighted mean.  p0, v0, goal: (3, ld); spheres: (K, 4) rows (cx, cy, cz, r), same dtype, shared by all problems.
+        -> dict(U (3N, ld), cost (ld,) with the penalty at U, trace (iters, ld) | None = the minimum sample cost per iteration,
+        keys int64 (ld,) | None = the argmin key of each problem's cost).  U_out may be U (in place); iter_offset: int32 (1,) device
+        word added to iter_base (graph replays); ``out`` = (U_out, cost, trace, keys) reuses preallocated outputs."""
+        return self._mppi_call("mppi", (), params, p0, v0, goal, U, n_samples, iters, sigma, temperature, seed, iter_base,
+                               index_base, spheres, obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out)
+
+    def mppi_split_workspace(self, params: Params, nprob: int, splits: int):
+        """A workspace for :meth:`mppi_split` over `nprob` problems (float64 words; no initialisation needed)."""
+        return self.be.empty((max(self.lib.mppi_split_workspace_bytes(params.horizon, int(nprob), int(splits)) // 8, 1),), "f64")
+
+    def mppi_split(self, params: Params, p0, v0, goal, U, n_samples: int, iters: int, sigma: float, temperature: float, splits: int,
+                   seed: int = 0, iter_base: int = 0, index_base: int = 0, spheres=None, obstacle_weight: float = 0.0, U_out=None,
+                   want_trace: bool = True, want_keys: bool = True, iter_offset=None, B: Optional[int] = None, out=None, workspace=None):
+        """:meth:`mppi` with every problem's samples split over `splits` workgroups (``se3mpc_mppi_split_*``): `iters` + 1 launches, one
+        per iteration and one that finishes, so that one problem -- or a few -- uses many compute units.  Same operands, keywords and
+        returned dict as :meth:`mppi`; `n_samples` must be a multiple of 64 * `splits`.  The partial sums of the splits are folded in
+        split order, so the result differs from :meth:`mppi` in the last bits of the float64 sums only (``splits`` = 1: not at all).
+        ``workspace``: a float64 tensor of :meth:`mppi_split_workspace` to reuse (required under graph capture); None allocates one."""
+        ws = workspace
+        if ws is None:
+            self.be.check(U, "U")
+            ws = self.mppi_split_workspace(params, self._B(U.shape[1], B), splits)
+        else:
+            self.be.check(ws, "workspace")
+            if self.be.suffix(ws) != "f64":
+                raise ValueError("workspace: expected a float64 tensor of Ops.mppi_split_workspace")
+        tail = (int(splits), self.be.ptr(ws), int(np.prod(ws.shape)) * 8)
+        return self._mppi_call("mppi_split", tail, params, p0, v0, goal, U, n_samples, iters, sigma, temperature, seed, iter_base, index_base,
+                               spheres, obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out)
 
     def mppi_samples(self, params: Params, U, n_samples: int, sigma: float, seed: int = 0, iter_base: int = 0, index_base: int = 0,
                      want_noise: bool = False, want_raw: bool = False, B: Optional[int] = None):

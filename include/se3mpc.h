@@ -341,6 +341,31 @@ int se3mpc_mppi_f64(const se3mpc_params* p, int nprob, int ld, int S, int iters,
                     uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const double* p0, const double* v0, const double* goal,
                     const double* U_in, double* U_out, const double* spheres, int K, double obstacle_weight, double* cost, double* trace,
                     uint64_t* keys, void* stream);
+/* se3mpc_mppi_* with ONE problem's samples split over `splits` workgroups (split j owns samples [j S / splits, (j + 1) S / splits)), for
+ * the call that plans one or a few problems and would otherwise run on one or a few compute units.  Same operands, same noise (the
+ * counter (q, s, g, k) does not depend on who draws a sample), same cost, same update, same outputs as se3mpc_mppi_*; only the order of
+ * the float64 sums differs: each split sums its own samples as se3mpc_mppi_* does, and the splits' partial sums are folded in split
+ * order j = 0 .. splits - 1 against the running minimum.  splits = 1 gives the bytes of se3mpc_mppi_*.  Results are identical run to run
+ * and do not depend on how the device schedules the workgroups.
+ * The call enqueues iters + 1 launches on `stream` (one per iteration over a grid of splits x nprob workgroups, then one that writes
+ * U_out, cost, keys and the last trace row): the kernel boundary hands the partial sums of an iteration to the next.  It allocates
+ * nothing and synchronises nothing, so it can be captured into a graph; every launch reads *iter_offset and adds its own iteration
+ * number, so a replay advances as se3mpc_mppi_* does.  U_out may alias U_in.
+ * workspace: device memory of at least se3mpc_mppi_split_workspace_bytes(p->horizon, nprob, splits) bytes, 8-byte aligned.  It needs no
+ * initialisation and holds nothing between calls; two calls in flight at once need a workspace each.  iters = 0 does not touch it.
+ * Argument rules: everything se3mpc_mppi_* rejects, with the same codes; also SE3MPC_ERR_SHAPE for splits < 1, S not a multiple of
+ * 64 * splits (every split owns whole wavefronts), S / splits < 64, nprob > 65535 and workspace_bytes too small, and SE3MPC_ERR_NULL
+ * for workspace == NULL (the last two when iters > 0).  Every rejected call sets se3mpc_last_error and launches nothing.
+ * se3mpc_mppi_split_workspace_bytes returns 0 for arguments outside these rules. */
+size_t se3mpc_mppi_split_workspace_bytes(int horizon, int nprob, int splits);
+int se3mpc_mppi_split_f32(const se3mpc_params* p, int nprob, int ld, int S, int iters, double sigma, double temperature, uint64_t seed,
+                          uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const float* p0, const float* v0,
+                          const float* goal, const float* U_in, float* U_out, const float* spheres, int K, double obstacle_weight, float* cost,
+                          float* trace, uint64_t* keys, int splits, void* workspace, size_t workspace_bytes, void* stream);
+int se3mpc_mppi_split_f64(const se3mpc_params* p, int nprob, int ld, int S, int iters, double sigma, double temperature, uint64_t seed,
+                          uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const double* p0, const double* v0,
+                          const double* goal, const double* U_in, double* U_out, const double* spheres, int K, double obstacle_weight,
+                          double* cost, double* trace, uint64_t* keys, int splits, void* workspace, size_t workspace_bytes, void* stream);
 /* The samples of ONE iteration (g = iter_base) of se3mpc_mppi_*, materialised for inspection: column p * S + s of T_out [3N][ld_out]
  * (ld_out >= S * nprob) is T_s of problem p; noise: NULL or [3N][ld_out] = the normals n of that column (drawn for s = 0 too, where the
  * sample does not use them); raw: NULL or [4N][ld_out] = the Philox words, row 4k + j = x_j of step k.  Same argument rules. */

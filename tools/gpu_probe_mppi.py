@@ -1,7 +1,9 @@
 """MPPI probe: the batched launch (4096 problems x 256 samples x 8 iterations, N = 30, K = 0 / 16, f32 / f64; and N = 50,
 K = 16 next to the obstacle-aware gradient loop's yardstick), plan_mppi latency next to plan_shooting and plan_trajectory in the same
 process, and the (sigma, temperature, iters) tuning sweep on the obstacle scene and the cfg-2 distribution.  HIP events, warm-up as bench.py.
-  python tools/gpu_probe_mppi.py launch|plan|tune [--out FILE]      (one part per process: each GPU step under its own time limit)"""
+The split part: one problem, N = 30, f32 / f64, K = 0 / 16, S in {1024, 4096, 16384} x splits in {unsplit, 1 .. 64}: the
+captured plan (wall clock to the synchronise, as the plan part) and the bare launches (HIP events); then B in {1, 16, 256} x S = 1024.
+  python tools/gpu_probe_mppi.py launch|plan|tune|split [--out FILE]      (one part per process: each GPU step under its own time limit)"""
 import argparse
 import json
 import os
@@ -121,14 +123,94 @@ def tune_part(ops):
     return rows
 
 
+def split_part(ops, reps=200, warmup=20, iters=8):
+    """Split-sample MPPI against the one-workgroup path, same process, warm: rows of kind "plan" (plan_mppi through its captured graph, host
+    clock around the call, which ends in a synchronise), "launch" (the iters + 1 launches of Ops.mppi_split / the one of Ops.mppi between HIP
+    events) and "batch" (the launches over B problems).  splits = None is the unsplit path."""
+    import torch
+    from dart_planner_amd.capi import Params
+    from dart_planner_amd.common.types import DroneState
+    from dart_planner_amd.planning.se3_mpc_planner import SE3MPCConfig, SE3MPCPlanner
+    N = 30
+    rng = np.random.default_rng(4)
+    spheres16 = np.concatenate([np.round(rng.uniform(0, 15, (16, 3)) * 2) / 2, np.ones((16, 1))], axis=1)
+    st = DroneState(timestamp=0.0, position=np.array([0.0, 0.0, 1.0]), velocity=np.zeros(3))
+    goal = np.array([4.0, 2.0, 2.0])
+    rows = []
+
+    def emit(**row):
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    def pcts(ts, unit):
+        return {f"p50_{unit}": float(np.percentile(ts, 50)), f"p95_{unit}": float(np.percentile(ts, 95))}
+
+    def event_times(go):
+        for _ in range(warmup):
+            go()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); go(); e1.record(); e1.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3)
+        return ts
+
+    def operands(B, S, tdt, K):
+        prm = Params.reference_defaults(horizon=N, dt=0.1)
+        r = np.random.default_rng(2)
+        lane = lambda a: torch.tensor(np.ascontiguousarray(np.asarray(a, float).reshape(B, -1).T), dtype=tdt, device="cuda:0")
+        p0, v0, gl = lane(r.uniform(-2, 2, (B, 3)) + [0, 0, 2]), lane(r.uniform(-1, 1, (B, 3))), lane(r.uniform(-4, 4, (B, 3)) + [0, 0, 2])
+        U = lane(np.tile([0.0, 0.0, 14.715], (B, N, 1)))
+        sph = torch.tensor(spheres16, dtype=tdt, device="cuda:0") if K else None
+        out = (torch.empty_like(U), torch.empty(B, dtype=tdt, device="cuda:0"), torch.empty((iters, B), dtype=tdt, device="cuda:0"),
+               torch.empty(B, dtype=torch.int64, device="cuda:0"))
+        return prm, p0, v0, gl, U, sph, out
+
+    def launcher(B, S, tdt, K, g):
+        prm, p0, v0, gl, U, sph, out = operands(B, S, tdt, K)
+        kw = dict(seed=1, spheres=sph, obstacle_weight=1000.0, out=out)
+        if g is None:
+            return lambda: ops.mppi(prm, p0, v0, gl, U, S, iters, 4.0, 100.0, **kw)
+        ws = ops.mppi_split_workspace(prm, B, g)
+        return lambda: ops.mppi_split(prm, p0, v0, gl, U, S, iters, 4.0, 100.0, g, workspace=ws, **kw)
+
+    valid = lambda S, g: g is None or (S % (64 * g) == 0 and S // g >= 64)
+    for precision in ("f32", "f64"):
+        tdt = torch.float32 if precision == "f32" else torch.float64
+        for K in (0, 16):
+            pl = SE3MPCPlanner(SE3MPCConfig(prediction_horizon=N), device="cuda:0")
+            for c in spheres16[:K]:
+                pl.add_obstacle(c[:3], float(c[3]))
+            for S in (1024, 4096, 16384):
+                for g in (None, 1, 2, 4, 8, 16, 32, 64):
+                    if not valid(S, g):
+                        continue
+                    ts = []
+                    for i in range(warmup + reps):
+                        t0 = time.perf_counter()
+                        pl.plan_mppi(st, goal, n_samples=S, iters=iters, precision=precision, splits=g)
+                        torch.cuda.synchronize()
+                        if i >= warmup:
+                            ts.append((time.perf_counter() - t0) * 1e3)
+                    emit(kind="plan", dtype=precision, K=K, N=N, samples=S, iters=iters, splits=g, auto=pl._mppi_splits("auto", S), **pcts(ts, "ms"))
+                    emit(kind="launch", dtype=precision, K=K, N=N, samples=S, iters=iters, splits=g, problems=1,
+                         **pcts(event_times(launcher(1, S, tdt, K, g)), "us"))
+    for B in (1, 16, 256):
+        for g in (None, 1, 2, 4, 8, 16):
+            emit(kind="batch", dtype="f32", K=0, N=N, samples=1024, iters=iters, splits=g, problems=B, auto=SE3MPCPlanner._mppi_splits("auto", 1024, B),
+                 **pcts(event_times(launcher(B, 1024, torch.float32, 0, g)), "us"))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=["launch", "plan", "tune"])
+    ap.add_argument("part", choices=["launch", "plan", "tune", "split"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from dart_planner_amd.ops import Ops, TorchBackend
     ops = Ops(TorchBackend("cuda:0"))
-    rows = launch_part(ops) if a.part == "launch" else plan_part() if a.part == "plan" else tune_part(ops)
+    rows = {"launch": lambda: launch_part(ops), "plan": plan_part, "tune": lambda: tune_part(ops), "split": lambda: split_part(ops)}[a.part]()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         json.dump(rows, open(a.out, "w"), indent=1)

@@ -5,7 +5,10 @@ What the reference's closed-loop tests do one drone and one Python call at a tim
 per planning cycle for B drones: ``se3mpc_solve_*`` (every drone re-plans from its own state) and ``se3mpc_closed_loop_*``
 (``substeps`` control + simulator steps against the fresh plan, which is read in place from the solver's outputs).  No host
 arithmetic, no copies between the two; the only host work per cycle is the N plan stamps (planner.py:661: start + arange(N)*dt).
+``run_mppi`` / ``run_mppi_fused`` close the same loop with MPPI as the planner (``se3mpc_mppi_closed_loop_*``: plan, control and simulate
+inside one kernel, the plan handed over in LDS).
 """
+import math
 from typing import Optional
 
 from ..capi import ControllerParams, Params, SimulatorParams
@@ -65,6 +68,80 @@ class ClosedLoopMonteCarlo:
         if int(ops.be.to_host(out["overflowed"])[0]) != 0:
             return self.run(p0, v0, goal, cycles, substeps, sim_dt, wind=wind)
         return dict(pos=pos, vel=vel, att=att, omega=om, time=time, controller_state=st, logs=[], last_plan=out if want_last_plan else None)
+
+    def resolve_shift(self, substeps: int, sim_dt: float, shift: Optional[int] = None) -> int:
+        """Rows the MPPI nominal moves forward per planning cycle.  None: the plan steps one act phase covers, rounded half up,
+        ``floor(substeps * sim_dt / params.dt + 0.5)`` clipped to [0, N]."""
+        N = self.params.horizon
+        if shift is None:
+            shift = int(math.floor(substeps * sim_dt / self.params.dt + 0.5))
+        return max(0, min(N, int(shift)))
+
+    def _mppi_start(self, p0, v0, nominal):
+        import torch
+        ops, prm = self.ops, self.params
+        B, N = p0.shape[0], prm.horizon
+        pos, vel = p0.clone(), v0.clone()
+        att, om = torch.zeros_like(p0), torch.zeros_like(p0)
+        time = torch.zeros(B, dtype=torch.float64, device=ops.be.device)
+        st = ops.controller_state(self.controller, B)
+        if nominal is None:
+            U = torch.zeros(B, N, 3, dtype=p0.dtype, device=ops.be.device)
+            U[:, :, 2] = prm.mass * prm.gravity
+        else:
+            U = nominal.clone()
+        return pos, vel, att, om, time, st, U
+
+    def run_mppi(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
+                 seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None, nominal=None,
+                 log: bool = False):
+        """The receding-horizon Monte-Carlo with MPPI as the planner (``se3mpc_mppi_closed_loop_*``), one call per planning cycle: each
+        cycle runs `iters` MPPI iterations of `n_samples` samples from the drone's own state on its nominal thrust sequence (hover, or
+        `nominal` (B, N, 3)), hands the plan to the controller on the chip, takes `substeps` control + simulator steps and moves the
+        nominal forward by `shift` rows.  spheres: (K, 4) rows (cx, cy, cz, r) for the planner's penalty (`obstacle_weight`) and for the
+        clearance output.  shift=None resolves to ``floor(substeps * sim_dt / params.dt + 0.5)`` clipped to [0, N]: the plan steps one act
+        phase covers, rounded half up.
+        -> what :meth:`run` returns, plus U (B, N, 3) = the next cycle's nominal, cost (B,) at the last cycle's nominal, trace
+        (B, cycles, iters) = the minimum sample cost per iteration, clearance (B,) = min over every simulator step and sphere of
+        |pos - c| - r (None without spheres); logs = [dict(plan_last, trace, cost)] per cycle if `log`."""
+        import torch
+        ops = self.ops
+        pos, vel, att, om, time, st, U = self._mppi_start(p0, v0, nominal)
+        sh = self.resolve_shift(substeps, sim_dt, shift)
+        logs, traces, out, clr = [], [], None, None
+        for c in range(cycles):
+            out = ops.mppi_closed_loop(self.params, self.controller, self.simulator, st, time, pos, vel, att, om, goal, U, 1, substeps, sim_dt,
+                                       n_samples, iters, sigma, temperature, seed=seed, cycle_base=c, shift=sh, spheres=spheres,
+                                       obstacle_weight=obstacle_weight, wind=wind, want_plan=log, clearance=clr)
+            clr = out["clearance"]
+            traces.append(out["trace"])
+            if log:
+                logs.append(dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"]))
+        trace = torch.cat(traces, dim=1) if traces else torch.zeros(p0.shape[0], 0, max(int(iters), 0), dtype=p0.dtype, device=ops.be.device)
+        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, controller_state=st, logs=logs, U=U, cost=None if out is None else out["cost"],
+                    trace=trace, clearance=clr)
+
+    def run_mppi_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float,
+                       temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None,
+                       nominal=None, log: bool = False):
+        """:meth:`run_mppi` in ONE launch: every drone's `cycles` planning cycles inside one kernel, the plan never leaving the chip.  Same
+        code, same bits as :meth:`run_mppi`, same arguments and the same shift rule (shift=None: ``floor(substeps * sim_dt / params.dt +
+        0.5)`` clipped to [0, N]).  `log` keeps the last cycle's plan only: logs = [dict(plan_last, trace, cost)] with one entry.
+
+        Measured on an MI355X (256 samples, 8 iterations, N = 30, 33 cycles x 15 steps): at 256 drones this is the fastest
+        form, 9 - 16 % ahead of the per-cycle chain of se3mpc_mppi_* + se3mpc_rollout_cost_grad_* + se3mpc_extract_* + se3mpc_closed_loop_*.
+        At 4096 drones it is 17 - 27 % SLOWER than that chain (the kernel holds the controller's registers, so the MPPI phase runs at three
+        (float32) / two (float64) wavefronts per SIMD instead of four, and one lane per workgroup flies while the others wait): for thousands of
+        drones drive the chain (``tools/gpu_probe_mppi_closed_loop.py``, ``chain_form``) unless the clearance output is what you need."""
+        ops = self.ops
+        pos, vel, att, om, time, st, U = self._mppi_start(p0, v0, nominal)
+        sh = self.resolve_shift(substeps, sim_dt, shift)
+        out = ops.mppi_closed_loop(self.params, self.controller, self.simulator, st, time, pos, vel, att, om, goal, U, cycles, substeps, sim_dt,
+                                   n_samples, iters, sigma, temperature, seed=seed, cycle_base=0, shift=sh, spheres=spheres,
+                                   obstacle_weight=obstacle_weight, wind=wind, want_plan=log)
+        logs = [dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"])] if log else []
+        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, controller_state=st, logs=logs, U=U, cost=out["cost"], trace=out["trace"],
+                    clearance=out["clearance"])
 
     def capture(self, B: int, dtype, cycles: int, substeps: int, sim_dt: float, with_wind: bool = True):
         """The whole Monte-Carlo (2 x `cycles` kernel launches + the plan stamps) captured ONCE into a hipGraph; each call of the

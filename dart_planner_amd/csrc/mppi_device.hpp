@@ -120,6 +120,18 @@ __device__ __forceinline__ void roll_step(const Ctx<R>& c, Roll<R>& r, int k, co
   }
 }
 
+// The state recurrence of roll_step alone, for a caller that wants the trajectory and not the cost: (p, v) advance by one step under
+// thrust t, acc = the acceleration roll_step forms from t
+template <typename R>
+__device__ __forceinline__ void roll_state_step(const DevParams<R>& q, R p[3], R v[3], const R t[3], R acc[3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    acc[a] = t[a] * q.inv_mass - ((a == 2) ? q.grav : (R)0);
+    p[a] = p[a] + v[a] * q.dt + q.half_dt2 * acc[a];
+    v[a] = v[a] + acc[a] * q.dt;
+  }
+}
+
 template <typename R>
 __device__ __forceinline__ Roll<R> roll_begin(const Ctx<R>& c) {
   Roll<R> r;
@@ -241,6 +253,20 @@ __device__ __forceinline__ double weighted_pass(const Ctx<R>& c, const R* U, int
     __syncthreads();
   }
   return m;
+}
+
+// The receding-horizon warm start of the nominal in LDS, by the whole workgroup: U[k] <- U[k + shift] for k < N - shift, (0, 0, hover) for
+// the rows behind (shift = 0 keeps U, shift = N resets it).  tmp: LDS scratch of 3N values; U is visible to every lane on return.
+template <typename R>
+__device__ __forceinline__ void shift_nominal(const DevParams<R>& q, R* U, R* tmp, int shift) {
+  const int rows = 3 * q.N;
+  for (int r = (int)threadIdx.x; r < rows; r += (int)blockDim.x) {
+    const int src = r + 3 * shift;
+    tmp[r] = src < rows ? U[src] : ((r % 3 == 2) ? q.hover : (R)0);
+  }
+  __syncthreads();
+  for (int r = (int)threadIdx.x; r < rows; r += (int)blockDim.x) U[r] = tmp[r];
+  __syncthreads();
 }
 
 // Cost and argmin key of the nominal as it stands, written by lane 0 of the calling wavefront (the tail of every MPPI entry point)

@@ -634,6 +634,60 @@ class Ops:
                            self.be.ptr(X), self.be.ptr(acc), self.be.ptr(info), self.be.ptr(over), self.be.stream())
         return dict(overflowed=over, x=X, accelerations=acc, info=info)
 
+    def mppi_closed_loop(self, params: Params, cp: ControllerParams, sp: SimulatorParams, state, time, pos, vel, att, omega, goal, U,
+                         cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
+                         seed: int = 0, cycle_base: int = 0, shift: int = 1, iter_base: int = 0, index_base: int = 0, spheres=None,
+                         obstacle_weight: float = 0.0, wind=None, want_trace: bool = True, want_plan: bool = False, clearance=None,
+                         want_clearance: bool = True):
+        """se3mpc_mppi_closed_loop_*: `cycles` x (`iters` MPPI iterations from the drone's own state on its nominal, the plan handed to the
+        controller on the chip, `substeps` control + simulator steps, the nominal shifted by `shift` rows) for B drones in ONE launch, in
+        place on (state, time, pos, vel, att, omega) and on the nominals U (B, N, 3).  goal (B, 3); spheres (K, 4) rows (cx, cy, cz, r)
+        shared by all drones; wind None, (3,) or (B, 3) newtons.  clearance: a (B,) running minimum to continue (updated in place), or None:
+        a fresh one at +inf when `want_clearance` and there are spheres.
+        -> dict(U (B, N, 3) = the next cycle's starting nominal, cost (B,) at the last cycle's nominal, trace (B, cycles, iters) | None,
+        plan_last (B, 3, N, 3) = P, V, A of the last cycle's plan | None, clearance (B,) | None)."""
+        B = pos.shape[0]
+        suf = self.be.suffix(pos)
+        N = params.horizon
+        for a, nm in ((pos, "pos"), (vel, "vel"), (att, "att"), (omega, "omega"), (goal, "goal")):
+            self._rows3(a, B, nm, suf)
+        self.be.check(state, "state"); self.be.check(time, "time"); self.be.check(U, "U")
+        if tuple(state.shape) != (B, CONTROLLER_STATE_WORDS) or self.be.suffix(state) != "f64" or tuple(time.shape) != (B,) or self.be.suffix(time) != "f64":
+            raise ValueError("state: float64 (B, 12); time: float64 (B,)")
+        if tuple(U.shape) != (B, N, 3) or self.be.suffix(U) != suf:
+            raise ValueError(f"U: expected ({B}, {N}, 3) {suf}, got {tuple(U.shape)}")
+        w_stride = 0
+        if wind is not None:
+            self.be.check(wind, "wind")
+            if self.be.suffix(wind) != suf or wind.shape[-1] != 3 or (wind.ndim == 2 and wind.shape[0] != B):
+                raise ValueError("wind: (3,) or (B, 3)")
+            w_stride = 3 if wind.ndim == 2 else 0
+        K = 0
+        if spheres is not None:
+            self.be.check(spheres, "spheres")
+            if spheres.ndim != 2 or spheres.shape[1] != 4 or spheres.shape[0] > SE3MPC_MAX_SPHERES or self.be.suffix(spheres) != suf:
+                raise ValueError(f"spheres: expected (K<={SE3MPC_MAX_SPHERES}, 4) {suf}, got {tuple(spheres.shape)}")
+            K = spheres.shape[0]
+        if clearance is not None:
+            self.be.check(clearance, "clearance")
+            if tuple(clearance.shape) != (B,) or self.be.suffix(clearance) != suf:
+                raise ValueError(f"clearance: expected ({B},) {suf}")
+        elif want_clearance and K:
+            clearance = self.be.empty((B,), suf)
+            clearance[...] = float("inf")
+        cost = self.be.empty((B,), suf)
+        trace = self.be.empty((B, max(int(cycles), 1), max(int(iters), 1)), suf) if want_trace else None
+        plan = self.be.empty((B, 3, N, 3), suf) if want_plan else None
+        self.lib.loop_call("mppi_closed_loop", suf, params, cp, sp, B, int(cycles), int(substeps), float(sim_dt), int(cycle_base) & 0xFFFFFFFF,
+                           int(shift), int(n_samples), int(iters), float(sigma), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                           int(iter_base) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF, self.be.ptr(goal), self.be.ptr(spheres if K else None), K,
+                           float(obstacle_weight), self.be.ptr(wind), w_stride, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel),
+                           self.be.ptr(att), self.be.ptr(omega), self.be.ptr(state), self.be.ptr(U), self.be.ptr(cost), self.be.ptr(trace),
+                           self.be.ptr(plan), self.be.ptr(clearance), self.be.stream())
+        if trace is not None and (cycles <= 0 or iters <= 0):
+            trace = trace[:, :max(int(cycles), 0), :max(int(iters), 0)]
+        return dict(U=U, cost=cost, trace=trace, plan_last=plan, clearance=clearance)
+
     def controller_integral_update(self, cp: ControllerParams, state, vel_error, dt: float, saturation=None) -> None:
         """_update_integral_error(vel_error, dt, thrust_saturated, torque_saturated) (controller.py:536-564) for B drones, in place on
         `state`.  saturation: int32 (B,) bit 0 thrust, bits 1..3 torque x/y/z, or None."""

@@ -643,6 +643,41 @@ int se3mpc_monte_carlo_f64(const se3mpc_params* p, const se3mpc_controller_param
                            double* pos, double* vel, double* att, double* omega, double* state, double* X_last, double* acc_last,
                            se3mpc_solve_info* info_last, int32_t* overflowed, void* stream);
 
+/* The receding-horizon closed-loop Monte-Carlo with se3mpc_mppi_* as its planner, in ONE launch (one workgroup of min(S, 256) lanes per
+ * drone; no atomics, no workspace, no allocation, no synchronise).  Everything is in problem layout: goal [B][3] (input); time [B],
+ * pos / vel / att / omega [B][3], state [B][SE3MPC_CONTROLLER_STATE_WORDS]: in / out as se3mpc_monte_carlo_*; wind, wind_stride as
+ * se3mpc_monte_carlo_*; spheres [K][4] rows (cx, cy, cz, r) shared by all drones as se3mpc_mppi_*; U [B][N][3]: in / out, each drone's
+ * nominal thrust sequence.  Cycle c = 0 .. cycles - 1 of drone b, with C = cycle_base + c and q = index_base + b:
+ *   plan       `iters` iterations of se3mpc_mppi_* (same noise, clip, cost, sphere penalty and float64 update in the same order, hence the
+ *              same bits) from the drone's current (pos, vel) on U, iteration number g = iter_base + C * iters + i (uint32 wrap);
+ *              trace[b][c][i] = the minimum sample cost; in the last cycle cost[b] = the cost (with the penalty) of the updated U
+ *   hand over  the updated U rolled out in the entry point's type: plan row k = the state BEFORE step k (row 0 = the drone's state),
+ *              A_k = U_k / mass - (0, 0, g), stamped (C * substeps * sim_dt) + k * params->dt.  The plan stays on the chip; the last
+ *              cycle's goes to plan_last [B][3][N][3] (P, V, A) when given
+ *   act        `substeps` x the step of se3mpc_closed_loop_* (plan sample -> compute_control with yaw 0 -> DroneSimulator.step at
+ *              sim_dt; no gust, no stop at the plan's end) -- the same code, hence the same bits
+ *   clearance  (clearance != NULL and K > 0) after every simulator step clearance[b] = min(clearance[b], min_j(|pos - c_j| - r_j)),
+ *              raw radii, no margin; the caller initialises the array (normally +inf)
+ *   warm start U[k] <- U[k + shift] for k < N - shift, (0, 0, mass * gravity) for the rows behind; 0 <= shift <= N (0 keeps U, N resets it)
+ * so U on return is the next cycle's starting nominal, and one call with cycles = C equals C calls with cycles = 1 and cycle_base =
+ * 0 .. C - 1, bit for bit.  trace: NULL or [B][cycles][iters]; plan_last, clearance: NULL or as above.
+ * Argument rules: everything se3mpc_mppi_* and se3mpc_monte_carlo_* reject, with the same codes (S a multiple of 64 in [64, 65536], K in
+ * [0, SE3MPC_MAX_SPHERES]: SE3MPC_ERR_SHAPE; sigma >= 0, temperature > 0, obstacle_weight >= 0 and sim_dt finite: SE3MPC_ERR_PARAM);
+ * shift outside [0, N], iters < 0, cycles < 0, substeps < 0, B < 0: SE3MPC_ERR_SHAPE; a NULL required operand: SE3MPC_ERR_NULL.  B = 0
+ * and cycles = 0 are no-ops.  Every rejected call sets se3mpc_last_error and launches nothing. */
+int se3mpc_mppi_closed_loop_f32(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B,
+                                int cycles, int substeps, double sim_dt, uint32_t cycle_base, int shift, int S, int iters, double sigma,
+                                double temperature, uint64_t seed, uint32_t iter_base, uint32_t index_base, const float* goal,
+                                const float* spheres, int K, double obstacle_weight, const float* wind, long long wind_stride, double* time,
+                                float* pos, float* vel, float* att, float* omega, double* state, float* U, float* cost, float* trace,
+                                float* plan_last, float* clearance, void* stream);
+int se3mpc_mppi_closed_loop_f64(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B,
+                                int cycles, int substeps, double sim_dt, uint32_t cycle_base, int shift, int S, int iters, double sigma,
+                                double temperature, uint64_t seed, uint32_t iter_base, uint32_t index_base, const double* goal,
+                                const double* spheres, int K, double obstacle_weight, const double* wind, long long wind_stride, double* time,
+                                double* pos, double* vel, double* att, double* omega, double* state, double* U, double* cost, double* trace,
+                                double* plan_last, double* clearance, void* stream);
+
 /* ------------------------------------------------------------------ problem layout: [b][row]
  * The batched solve: replaces _solve_se3_mpc (planner.py:230-280) = cold start (or a caller
  * x0), box, scipy.optimize.minimize(method="L-BFGS-B", jac=..., bounds=..., maxiter, gtol,

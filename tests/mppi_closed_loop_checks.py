@@ -1,0 +1,413 @@
+"""Checks of the closed-loop MPPI Monte-Carlo (se3mpc_mppi_closed_loop_*, Ops.mppi_closed_loop, ClosedLoopMonteCarlo.run_mppi /
+run_mppi_fused) shared by the host-emulation suite (tests/test_emu_mppi_closed_loop.py) and the MI355X suite
+(tests/test_gpu_mppi_closed_loop.py).  Every check takes a parity_checks.Harness whose arrays are torch tensors (CPU tensors on the
+emulated library, HIP tensors on the device).
+
+Bounds (none of them new): U, cost and trace against the float64 oracle are those of tests/mppi_checks.py; the drone's state after a
+cycle is held to the closed-loop bounds of tests/controller_checks.py (f64 1e-8; f32 median over the drones 5e-3, every drone 5e-2);
+the plan rows to parity_checks' position / velocity / acceleration bounds."""
+import numpy as np
+
+import controller_checks as cc
+import mppi_checks as mc
+import mppi_oracle as mo
+from dart_planner_amd.capi import ControllerParams, Params, SimulatorParams
+from oracle import controller_oracle as co
+from oracle import se3mpc_oracle as orc
+
+STATE_KEYS = ("pos", "vel", "att", "omega", "time", "state", "U")
+F64_LOOP = 1e-8                   # controller_checks: closed loops, f64
+F32_LOOP_MEDIAN, F32_LOOP_EACH = 5e-3, 5e-2
+
+
+def bits_equal(a, b):
+    """torch.equal on the bit patterns (a fresh controller record holds NaN for "no last call")."""
+    import torch
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    as_int = {4: torch.int32, 8: torch.int64}[a.element_size()]
+    return torch.equal(a.contiguous().view(as_int), b.contiguous().view(as_int))
+
+
+class Scene:
+    """Operands of one batch of drones on the harness' backend, and the NumPy values the oracle starts from."""
+
+    def __init__(self, h, N, B, K=0, seed=5, dt=0.1, w_obs=40.0, wind="per_drone", sigma=1.0, lam=50.0, S=64, iters=2, prm=None, cp=None, sp=None,
+                 ccfg=None, sim=None, p0=None, v0=None, goal=None, U=None, sph=None):
+        rng = np.random.default_rng(seed + 1000)
+        prm0, cfg0, p0_, v0_, goal_, U_, sph_ = mc.problem(N, B, seed, dt=dt, K=K)
+        self.prm = prm if prm is not None else prm0
+        from parity_checks import oracle_cfg
+        self.cfg = oracle_cfg(self.prm)
+        r = lambda a: np.asarray(a, float).astype(h.dt).astype(float)
+        self.p0, self.v0, self.goal, self.U0 = (r(x if x is not None else y) for x, y in ((p0, p0_), (v0, v0_), (goal, goal_), (U, U_)))
+        self.sph = r(sph if sph is not None else sph_)
+        self.K = len(self.sph)
+        self.h, self.N, self.B, self.S, self.iters, self.sigma, self.lam, self.seed = h, N, B, S, iters, sigma, lam, seed
+        self.w_obs = w_obs if self.K else 0.0
+        self.ccfg = ccfg if ccfg is not None else co.ControllerConfig()
+        self.sim = sim if sim is not None else co.SimulatorConfig()
+        self.cp = cp if cp is not None else ControllerParams.from_config(self.ccfg)
+        self.sp = sp if sp is not None else SimulatorParams.reference_defaults()
+        w = r(rng.normal(0, 1.0, (B, 3)))
+        self.wind = {"per_drone": w, "shared": w[0], None: None}[wind]
+        d = lambda a: h.to_dev(np.ascontiguousarray(np.asarray(a).astype(h.dt)))
+        self.d = d
+        self.goal_d = d(self.goal)
+        self.sph_d = d(self.sph) if self.K else None
+        self.wind_d = None if self.wind is None else d(self.wind)
+
+    def fresh(self, lo=0, hi=None, att=None, omega=None):
+        """Device state of drones [lo, hi): pos, vel, att, omega, time, controller record, nominal, clearance at +inf."""
+        h, d = self.h, self.d
+        hi = self.B if hi is None else hi
+        n = hi - lo
+        z = np.zeros((n, 3))
+        st = dict(pos=d(self.p0[lo:hi]), vel=d(self.v0[lo:hi]), att=d(z if att is None else att[lo:hi]), omega=d(z if omega is None else omega[lo:hi]),
+                  time=h.to_dev(np.zeros(n)), state=h.ops.controller_state(self.cp, n), U=d(self.U0[lo:hi]))
+        st["clearance"] = d(np.full(n, np.inf)) if self.K else None
+        return st
+
+    def call(self, st, cycles, substeps, sim_dt, shift, cycle_base=0, lo=0, hi=None, iter_base=0, **kw):
+        hi = self.B if hi is None else hi
+        S = kw.pop("S", self.S)
+        wind = self.wind_d
+        if wind is not None and wind.ndim == 2:
+            wind = wind[lo:hi].contiguous()
+        a = dict(seed=self.seed, cycle_base=cycle_base, shift=shift, iter_base=iter_base, index_base=lo, spheres=self.sph_d,
+                 obstacle_weight=self.w_obs, wind=wind, clearance=st["clearance"], want_plan=True)
+        a.update(kw)
+        return self.h.ops.mppi_closed_loop(self.prm, self.cp, self.sp, st["state"], st["time"], st["pos"], st["vel"], st["att"], st["omega"],
+                                           self.goal_d[lo:hi].contiguous(), st["U"], cycles, substeps, sim_dt, S, self.iters, self.sigma, self.lam, **a)
+
+
+def same_bits(a, b, what):
+    import torch
+    for k in STATE_KEYS + ("clearance",):
+        if a[k] is None and b[k] is None:
+            continue
+        assert bits_equal(a[k], b[k]), f"{what}: {k}"
+
+
+def check_cycle_equivalence(h, N, B, K, S=64, cycles=3, substeps=3, sim_dt=0.01, shift=1, wind="per_drone", seed=5):
+    """One call with cycles = C == C chained calls with cycles = 1 and cycle_base = 0 .. C - 1, bit for bit, on the whole state, U, the
+    clearance, the last cost and every trace row; drones [lo, hi) with index_base = lo == those rows of the full batch."""
+    import torch
+    sc = Scene(h, N, B, K=K, S=S, wind=wind, seed=seed)
+    one = sc.fresh()
+    o1 = sc.call(one, cycles, substeps, sim_dt, shift, iter_base=7)
+    many = sc.fresh()
+    for c in range(cycles):
+        oc = sc.call(many, 1, substeps, sim_dt, shift, cycle_base=c, iter_base=7)
+        assert bits_equal(oc["trace"][:, 0], o1["trace"][:, c]), f"trace of cycle {c}"
+    same_bits(one, many, "cycles = C vs C calls")
+    assert bits_equal(o1["cost"], oc["cost"]) and bits_equal(o1["plan_last"], oc["plan_last"]), "last cost / plan"
+    assert torch.isfinite(one["pos"]).all() and float((one["pos"] - sc.d(sc.p0)).abs().max()) > 0
+    if K:
+        assert torch.isfinite(one["clearance"]).all()
+    lo, hi = 1, B - 1
+    part = sc.fresh(lo, hi)
+    op = sc.call(part, cycles, substeps, sim_dt, shift, lo=lo, hi=hi, iter_base=7)
+    for k in STATE_KEYS + (("clearance",) if K else ()):
+        assert bits_equal(part[k], one[k][lo:hi]), f"slice [lo, hi): {k}"
+    assert bits_equal(op["cost"], o1["cost"][lo:hi]) and bits_equal(op["trace"], o1["trace"][lo:hi])
+    return o1
+
+
+def check_planner_inside(h, N, B, K, S=64, substeps=4, sim_dt=0.01, seed=6):
+    """(a) cycles = 1, shift = 0, substeps = 0: U, cost and trace are those of se3mpc_mppi_* on the transposed operands, bit for bit.
+    (b) plan_last against se3mpc_rollout_cost_grad_* (states) and se3mpc_extract_* (accelerations) at that U, to parity_checks' bounds.
+    (c) plan_last fed to se3mpc_closed_loop_* from the same initial state reproduces the entry point's `substeps` steps."""
+    import torch
+    sc = Scene(h, N, B, K=K, S=S, seed=seed)
+    rng = np.random.default_rng(seed)
+    att0, om0 = rng.normal(0, 0.05, (B, 3)).astype(h.dt).astype(float), rng.normal(0, 0.1, (B, 3)).astype(h.dt).astype(float)
+    st = sc.fresh(att=att0, omega=om0)
+    before = {k: v.clone() for k, v in st.items() if v is not None}
+    out = sc.call(st, 1, 0, sim_dt, 0, iter_base=11)
+    for k in ("pos", "vel", "att", "omega", "time", "state"):
+        assert bits_equal(st[k], before[k]), f"substeps = 0 leaves {k}"
+    run = mc.Run(h, sc.prm, sc.p0, sc.v0, sc.goal, sc.U0, sc.sph if K else None, sc.w_obs)
+    ref = run(S, sc.iters, sc.sigma, sc.lam, seed=sc.seed, iter_base=11)
+    lane_U = ref["U"].T.reshape(B, N, 3)
+    assert bits_equal(st["U"], lane_U.contiguous()), "U == se3mpc_mppi_*"
+    assert bits_equal(out["cost"], ref["cost"]), "cost == se3mpc_mppi_*"
+    assert bits_equal(out["trace"][:, 0].T.contiguous(), ref["trace"]), "trace == se3mpc_mppi_*"
+    # (b)
+    _, _, P, V = h.ops.rollout_cost_grad(sc.prm, run.p0, run.v0, run.goal, ref["U"], want_grad=False, want_states=True)
+    A = h.ops.extract(sc.prm, ref["U"])[0]
+    plan = h.to_host(out["plan_last"]).astype(float)
+    for i, (nm, dev) in enumerate((("P", P), ("V", V), ("A", A))):
+        want = h.unlane(dev, (B, N, 3))
+        err = float(np.max(np.abs(plan[:, i] - want)))
+        print(f"plan_last {nm}: max abs err {err:.3e} (bound {h.tol['pos']:.0e})")
+        assert err <= h.tol["pos"], (nm, err)
+    assert np.array_equal(plan[:, 0, 0], sc.p0) and np.array_equal(plan[:, 1, 0], sc.v0), "row 0 is the drone's state"
+    # (c) the act phase == se3mpc_closed_loop_* on the handed-over plan
+    st2 = sc.fresh(att=att0, omega=om0)
+    out2 = sc.call(st2, 1, substeps, sim_dt, 0, iter_base=11)
+    assert bits_equal(out2["plan_last"], out["plan_last"])
+    pl = out["plan_last"]
+    ref_st = sc.fresh(att=att0, omega=om0)
+    stamps = h.to_dev(np.arange(N) * sc.prm.dt)
+    h.ops.closed_loop(sc.cp, sc.sp, ref_st["state"], ref_st["time"], ref_st["pos"], ref_st["vel"], ref_st["att"], ref_st["omega"], stamps,
+                      pl[:, 0].contiguous(), pl[:, 1].contiguous(), pl[:, 2].contiguous(), nsteps=substeps, sim_dt=sim_dt, wind=sc.wind_d,
+                      stop_at_plan_end=False)
+    tol = F64_LOOP if h.dt == np.float64 else F32_LOOP_MEDIAN
+    for k in ("pos", "vel", "att", "omega", "time", "state"):
+        err = float((st2[k].double() - ref_st[k].double()).abs().max())
+        print(f"act phase vs se3mpc_closed_loop: {k} max abs err {err:.3e}")
+        assert err <= tol, (k, err)
+
+
+def oracle_cycle(sc, s, C, substeps, sim_dt, shift, iter_base=0, index_base=0, dtype=np.float64):
+    """One cycle of the float64 NumPy chain mppi_oracle.mppi -> se3mpc_oracle.rollout -> controller_oracle.closed_loop from the state
+    `s` = dict(pos, vel, att, omega, time, ctrl (ControllerState), U, clearance); returns the new state and (cost, trace, P, V, A)."""
+    cfg, N, B = sc.cfg, sc.N, len(s["pos"])
+    Un, cost, trace = np.zeros((B, N, 3)), np.zeros(B), np.zeros((B, sc.iters))
+    for b in range(B):
+        Un[b], cost[b], trace[b] = mo.mppi(s["pos"][b], s["vel"][b], sc.goal[index_base + b], s["U"][b], index_base + b, sc.S, sc.iters, sc.sigma,
+                                           sc.lam, sc.seed, cfg, iter_base=(iter_base + C * sc.iters) & 0xFFFFFFFF,
+                                           spheres=sc.sph if sc.K else None, obstacle_weight=sc.w_obs, dtype=dtype)
+    P, V = orc.rollout(s["pos"], s["vel"], Un, cfg)
+    A = Un / cfg.mass - cfg.gravity * np.array([0.0, 0.0, 1.0])
+    stamps = (C * substeps * sim_dt) + np.arange(N) * cfg.dt
+    ctrl = s["ctrl"].copy()
+    wind = None if sc.wind is None else (sc.wind if sc.wind.ndim == 1 else sc.wind[index_base:index_base + B])
+    new = dict(s, ctrl=ctrl, U=None)
+    clr = s["clearance"].copy()
+    if substeps > 0:
+        fin, log = co.closed_loop(sc.ccfg, sc.sim, ctrl, s["pos"], s["vel"], s["att"], s["omega"], s["time"], stamps, P, V, A, substeps, sim_dt,
+                                  wind=wind, stop_at_plan_end=False)
+        new.update(pos=fin["pos"], vel=fin["vel"], att=fin["att"], omega=fin["omega"], time=fin["t"])
+        if sc.K:
+            visited = np.concatenate([log["pos"][1:], fin["pos"][None]], axis=0)                    # after every simulator step
+            dist = np.linalg.norm(visited[:, :, None, :] - sc.sph[None, None, :, :3], axis=-1) - sc.sph[:, 3]
+            clr = np.minimum(clr, dist.min(axis=(0, 2)))
+    hover = np.array([0.0, 0.0, cfg.mass * cfg.gravity])
+    new["U"] = np.concatenate([Un[:, shift:], np.tile(hover, (B, shift, 1))], axis=1)
+    new["clearance"] = clr
+    return new, (cost, trace, P, V, A, Un)
+
+
+def device_state_to_oracle(sc, st):
+    h = sc.h
+    f = lambda a: h.to_host(a).astype(float).copy()
+    B = st["pos"].shape[0]
+    return dict(pos=f(st["pos"]), vel=f(st["vel"]), att=f(st["att"]), omega=f(st["omega"]), time=f(st["time"]),
+                ctrl=cc.state_to_oracle(f(st["state"]), sc.ccfg), U=f(st["U"]),
+                clearance=f(st["clearance"]) if st["clearance"] is not None else np.full(B, np.inf))
+
+
+def check_against_oracle(h, N, B, K, S=64, cycles=3, substeps=3, sim_dt=0.01, shift=1, seed=8):
+    """Cycle by cycle against the float64 NumPy chain started from the device's own state before the cycle (errors do not compound).
+    U, cost, trace: the bounds of mppi_checks.  State after the cycle: f64 1e-8; f32 the closed-loop bounds of controller_checks
+    (median over the drones 5e-3, every drone 5e-2).  The f32 bound needs no widening for the 2e-3 N the float32 nominal may differ by:
+    delta = 2e-3 N is delta / m = 1.3e-3 m/s^2 of planned acceleration; the act phase of tau = substeps * sim_dt <= 0.15 s samples plan
+    rows up to t = 0.2 s, where the planned velocity differs by <= 2.7e-4 m/s and the position by <= 2.7e-5 m; through the position gains
+    (kp 20, kd 10) that is <= 5e-3 m/s^2 of commanded acceleration, i.e. a thrust direction off by 5e-4 rad, which the attitude law
+    (kp 18 on a simulator inertia of 0.1) turns into <= 0.09 rad/s^2: <= 1.4e-2 rad/s of body rate over tau, <= 1e-3 rad of attitude,
+    <= 7e-4 m/s and <= 5e-5 m.  The largest of these, 1.4e-2, is inside the 5e-2 every drone is held to.
+    Clearance: against the minimum over the positions the oracle's closed loop visited, to the positions' bound."""
+    sc = Scene(h, N, B, K=K, S=S, seed=seed)
+    st = sc.fresh()
+    f32 = h.dt == np.float32
+    for c in range(cycles):
+        s0 = device_state_to_oracle(sc, st)
+        out = sc.call(st, 1, substeps, sim_dt, shift, cycle_base=c, iter_base=3)
+        ref, (cost, trace, P, V, A, Un) = oracle_cycle(sc, s0, c, substeps, sim_dt, shift, iter_base=3, dtype=h.dt)
+        Ud, cd, trd = h.to_host(st["U"]).astype(float), h.to_host(out["cost"]).astype(float), h.to_host(out["trace"]).astype(float)[:, 0]
+        plan = h.to_host(out["plan_last"]).astype(float)
+        if f32:
+            errU = np.max(np.abs(Ud - ref["U"]))
+            assert errU <= mc.F32_U_ABS, f"cycle {c}: U {errU}"
+            Udev = plan[:, 2] * sc.cfg.mass + [0.0, 0.0, sc.cfg.mass * sc.cfg.gravity]                # the nominal the kernel evaluated
+            for b in range(B):
+                c_at = mo.cost(s0["pos"][b], s0["vel"][b], sc.goal[b], Udev[b], sc.cfg, sc.sph if K else None, sc.w_obs)
+                assert abs(cd[b] - c_at) <= mc.F32_COST_REL * abs(c_at), f"cycle {c}: cost of drone {b}: {cd[b]} vs {c_at}"
+            assert np.all(np.abs(trd - trace) <= mc.F32_TRACE_REL * np.abs(trace)), f"cycle {c}: trace"
+        else:
+            assert np.max(np.abs(Ud - ref["U"])) <= mc.F64_REL * 25, f"cycle {c}: U"
+            assert np.all(np.abs(cd - cost) <= mc.F64_REL * np.abs(cost)), f"cycle {c}: cost"
+            assert np.all(np.abs(trd - trace) <= mc.F64_REL * np.abs(trace)), f"cycle {c}: trace"
+            assert np.max(np.abs(plan[:, 0] - P)) <= 1e-9 and np.max(np.abs(plan[:, 1] - V)) <= 1e-9 and np.max(np.abs(plan[:, 2] - A)) <= 1e-9
+        worst = np.zeros(B)
+        for k in ("pos", "vel", "att", "omega"):
+            worst = np.maximum(worst, np.max(np.abs(h.to_host(st[k]).astype(float) - ref[k]), axis=1))
+        print(f"cycle {c}: state error per drone {worst}")
+        if f32:
+            assert np.median(worst) <= F32_LOOP_MEDIAN and np.all(worst <= F32_LOOP_EACH), (c, worst)
+        else:
+            assert np.all(worst <= F64_LOOP), (c, worst)
+            assert np.max(np.abs(h.to_host(st["time"]) - ref["time"])) <= 1e-9
+        if K:
+            errc = np.max(np.abs(h.to_host(st["clearance"]).astype(float) - ref["clearance"]))
+            print(f"cycle {c}: clearance error {errc:.3e}")
+            assert errc <= (F32_LOOP_EACH if f32 else F64_LOOP), (c, errc)
+
+
+def behaviour_scene(h, B=4, N=15):
+    """Drones below a sphere of radius 1 m, goals straight above it, plan step 0.1 s.  The reference's DroneSimulator applies its thrust
+    along the world z axis whatever the attitude (simulator.py:59), so the drones can only climb: the scene is vertical, every drone's
+    line to its goal crosses the sphere (lateral offsets < r), and the planner's thrust box is narrowed to the near-vertical thrusts
+    this simulator can realise (max_tilt_angle 0.02 rad).  Planner, controller and simulator share mass 1 kg and g."""
+    prm = Params.reference_defaults(horizon=N, dt=0.1, mass=1.0, gravity=9.80665, max_thrust=20.0, max_tilt_angle=0.02)
+    ccfg = co.ControllerConfig()
+    sim = co.SimulatorConfig(mass=1.0, gravity=9.80665)
+    sp = SimulatorParams.reference_defaults(mass=1.0, gravity=9.80665)
+    off = (np.arange(B) - (B - 1) / 2) * 0.25
+    p0 = np.stack([off, np.zeros(B), np.full(B, 1.0)], axis=1)
+    goal = np.stack([off, np.zeros(B), np.full(B, 9.0)], axis=1)
+    sph = np.array([[0.0, 0.0, 5.0, 1.0]])
+    U = np.tile([0.0, 0.0, prm.mass * prm.gravity], (B, N, 1))
+    return dict(prm=prm, ccfg=ccfg, sim=sim, sp=sp, p0=p0, v0=np.zeros((B, 3)), goal=goal, sph=sph, U=U)
+
+
+BEHAVIOUR = dict(S=64, iters=2, sigma=3.0, lam=200.0, cycles=30, substeps=10, sim_dt=0.01, shift=1, w_obs=2000.0)
+
+
+def oracle_flight(sc, cycles, substeps, sim_dt, shift):
+    B = sc.B
+    s = dict(pos=sc.p0.copy(), vel=sc.v0.copy(), att=np.zeros((B, 3)), omega=np.zeros((B, 3)), time=np.zeros(B),
+             ctrl=co.ControllerState(B, sc.ccfg), U=sc.U0.copy(), clearance=np.full(B, np.inf))
+    for c in range(cycles):
+        s, _ = oracle_cycle(sc, s, c, substeps, sim_dt, shift)
+    return s
+
+
+_ORACLE_FLIGHTS = {}
+
+
+def check_behaviour(h, B=4, N=15, cycles=None):
+    """The scene of behaviour_scene flown with and without the sphere penalty.  The float64 NumPy chain itself must separate the two for
+    EVERY drone (minimum clearance < 0 without the penalty, > 0 with it) -- asserted first -- then the device must, and every drone ends
+    nearer its goal than it started."""
+    bs = behaviour_scene(h, B, N)
+    kw = dict(BEHAVIOUR, cycles=BEHAVIOUR["cycles"] if cycles is None else cycles)
+    res = {}
+    for w in (0.0, kw["w_obs"]):
+        sc = Scene(h, N, B, K=1, S=kw["S"], iters=kw["iters"], sigma=kw["sigma"], lam=kw["lam"], w_obs=w, wind=None, seed=21, **bs)
+        sc.w_obs = w
+        key = (B, N, kw["cycles"], w, np.dtype(h.dt).name)                             # computed once, shared by the tests that need it
+        if key not in _ORACLE_FLIGHTS:
+            _ORACLE_FLIGHTS[key] = oracle_flight(sc, kw["cycles"], kw["substeps"], kw["sim_dt"], kw["shift"])
+        ref = _ORACLE_FLIGHTS[key]
+        st = sc.fresh()
+        sc.call(st, kw["cycles"], kw["substeps"], kw["sim_dt"], kw["shift"])
+        res[w] = (ref, st, sc)
+        print(f"obstacle_weight {w}: oracle clearance {ref['clearance']}, device clearance {h.to_host(st['clearance'])}")
+    (r0, d0, sc0), (r1, d1, sc1) = res[0.0], res[kw["w_obs"]]
+    assert np.all(r0["clearance"] < 0) and np.all(r1["clearance"] > 0), "the oracle must separate the two runs for every drone"
+    c0, c1 = h.to_host(d0["clearance"]).astype(float), h.to_host(d1["clearance"]).astype(float)
+    assert np.all(c0 < 0), f"without the penalty every drone crosses the sphere: {c0}"
+    assert np.all(c1 > 0), f"with the penalty every drone keeps clear: {c1}"
+    for ref, st, sc in res.values():
+        start = np.linalg.norm(sc.p0 - sc.goal, axis=1)
+        end_dev = np.linalg.norm(h.to_host(st["pos"]).astype(float) - sc.goal, axis=1)
+        end_ref = np.linalg.norm(ref["pos"] - sc.goal, axis=1)
+        print(f"goal distance: start {start}, oracle end {end_ref}, device end {end_dev}")
+        assert np.all(end_ref < start) and np.all(end_dev < start)
+
+
+def check_determinism_and_dirty_buffers(h, N=6, B=3, K=2):
+    """Two runs give identical bytes; what trace and plan_last held before the call does not matter; a drone whose every sample cost is
+    NaN keeps its nominal (shift = 0)."""
+    import torch
+    sc = Scene(h, N, B, K=K, seed=4)
+    a, b = sc.fresh(), sc.fresh()
+    oa = sc.call(a, 2, 3, 0.01, 1)
+    ob = sc.call(b, 2, 3, 0.01, 1)
+    same_bits(a, b, "run to run")
+    for k in ("cost", "trace", "plan_last"):
+        assert bits_equal(oa[k], ob[k]), k
+    # dirty outputs: call the entry point with buffers full of NaN
+    d = sc.fresh()
+    suf = "f32" if h.dt == np.float32 else "f64"
+    be = h.ops.be
+    trace = sc.d(np.full((B, 2, sc.iters), np.nan)); plan = sc.d(np.full((B, 3, N, 3), np.nan)); cost = sc.d(np.full(B, np.nan))
+    h.ops.lib.loop_call("mppi_closed_loop", suf, sc.prm, sc.cp, sc.sp, B, 2, 3, 0.01, 0, 1, sc.S, sc.iters, sc.sigma, sc.lam, sc.seed, 0, 0,
+                        be.ptr(sc.goal_d), be.ptr(sc.sph_d), K, sc.w_obs, be.ptr(sc.wind_d), 3, be.ptr(d["time"]), be.ptr(d["pos"]), be.ptr(d["vel"]),
+                        be.ptr(d["att"]), be.ptr(d["omega"]), be.ptr(d["state"]), be.ptr(d["U"]), be.ptr(cost), be.ptr(trace), be.ptr(plan),
+                        be.ptr(d["clearance"]), be.stream())
+    same_bits(a, d, "dirty buffers")
+    assert bits_equal(trace, oa["trace"]) and bits_equal(plan, oa["plan_last"]) and bits_equal(cost, oa["cost"])
+    # a drone whose sample costs are all NaN
+    p0 = sc.p0.copy(); p0[1] = np.nan
+    sn = Scene(h, N, B, K=0, seed=4, p0=p0)
+    n = sn.fresh()
+    sn.call(n, 1, 0, 0.01, 0)
+    assert bits_equal(n["U"][1], sn.d(sn.U0)[1]), "an all-NaN drone keeps its nominal"
+    assert not bits_equal(n["U"][0], sn.d(sn.U0)[0])
+
+
+def check_invalid_arguments(h, N=6):
+    """Every rule of include/se3mpc.h returns its code, sets se3mpc_last_error and launches nothing."""
+    import torch
+    B = 2
+    sc = Scene(h, N, B, K=2, seed=1)
+    st = sc.fresh()
+    keep = {k: v.clone() for k, v in st.items()}
+    be, lib = h.ops.be, h.ops.lib
+    suf = "f32" if h.dt == np.float32 else "f64"
+    cost = sc.d(np.zeros(B))
+    ok = dict(prm=sc.prm, cp=sc.cp, sp=sc.sp, B=B, cycles=1, substeps=2, sim_dt=0.01, shift=1, S=64, iters=1, sigma=1.0, lam=1.0, goal=be.ptr(sc.goal_d),
+              spheres=be.ptr(sc.sph_d), K=2, w=1.0, wind=be.ptr(sc.wind_d), wstride=3, time=be.ptr(st["time"]), pos=be.ptr(st["pos"]),
+              state=be.ptr(st["state"]), U=be.ptr(st["U"]), cost=be.ptr(cost))
+
+    def status(**kw):
+        a = dict(ok, **kw)
+        return lib.loop_status("mppi_closed_loop", suf, a["prm"], a["cp"], a["sp"], a["B"], a["cycles"], a["substeps"], a["sim_dt"], 0, a["shift"],
+                               a["S"], a["iters"], a["sigma"], a["lam"], 0, 0, 0, a["goal"], a["spheres"], a["K"], a["w"], a["wind"], a["wstride"],
+                               a["time"], a["pos"], be.ptr(st["vel"]), be.ptr(st["att"]), be.ptr(st["omega"]), a["state"], a["U"], a["cost"],
+                               None, None, be.ptr(st["clearance"]), be.stream())
+
+    bad_cp = ControllerParams.from_config(sc.ccfg); bad_cp.mass = 0.0
+    bad_sp = SimulatorParams.reference_defaults(mass=-1.0)
+    nan, inf = float("nan"), float("inf")
+    cases = [(dict(S=0), -3), (dict(S=63), -3), (dict(S=96), -3), (dict(S=65536 + 64), -3), (dict(S=-64), -3), (dict(lam=0.0), -4),
+             (dict(lam=-1.0), -4), (dict(lam=nan), -4), (dict(lam=inf), -4), (dict(sigma=-0.5), -4), (dict(sigma=nan), -4), (dict(sigma=inf), -4),
+             (dict(K=-1), -3), (dict(K=257), -3), (dict(prm=sc.prm.copy(horizon=65)), -2), (dict(prm=sc.prm.copy(dt=0.0)), -4), (dict(prm=None), -1),
+             (dict(cp=None), -1), (dict(sp=None), -1), (dict(cp=bad_cp), -4), (dict(sp=bad_sp), -4), (dict(B=-1), -3), (dict(cycles=-1), -3),
+             (dict(substeps=-1), -3), (dict(iters=-1), -3), (dict(shift=-1), -3), (dict(shift=N + 1), -3), (dict(w=nan), -4), (dict(w=-1.0), -4),
+             (dict(w=inf), -4), (dict(sim_dt=nan), -4), (dict(sim_dt=inf), -4), (dict(wstride=2), -3), (dict(U=None), -1), (dict(spheres=None), -1),
+             (dict(goal=None), -1), (dict(time=None), -1), (dict(pos=None), -1), (dict(state=None), -1), (dict(cost=None), -1)]
+    for kw, want in cases:
+        got = status(**kw)
+        assert got == want, f"{kw}: {got} != {want}"
+        assert lib.last_error(), f"{kw}: se3mpc_last_error not set"
+    for k, v in keep.items():
+        assert bits_equal(st[k], v), f"a rejected call launched ({k})"
+    assert status(B=0, U=None) == 0 and status(cycles=0, U=None) == 0
+    for k, v in keep.items():
+        assert bits_equal(st[k], v), f"B = 0 / cycles = 0 are no-ops ({k})"
+    assert status(shift=0) == 0 and status(shift=N) == 0 and status(wind=None, wstride=0) == 0
+    assert not bits_equal(st["pos"], keep["pos"])
+
+
+def check_front_end(h, N=6, B=3, K=2):
+    """ClosedLoopMonteCarlo.run_mppi (one call per cycle) == run_mppi_fused (one call), bit for bit; the default shift rule; Ops' shape checks."""
+    import pytest
+    import torch
+    from dart_planner_amd.control.closed_loop import ClosedLoopMonteCarlo
+    sc = Scene(h, N, B, K=K, seed=2)
+    mcl = ClosedLoopMonteCarlo(h.ops, sc.prm)
+    assert mcl.resolve_shift(10, 0.01) == 1 and mcl.resolve_shift(4, 0.01) == 0 and mcl.resolve_shift(6, 0.01) == 1 and mcl.resolve_shift(16, 0.01) == 2
+    assert mcl.resolve_shift(1000, 0.01) == N and mcl.resolve_shift(3, 0.01, shift=4) == 4 and mcl.resolve_shift(3, 0.01, shift=99) == N
+    p0, v0 = sc.d(sc.p0), sc.d(sc.v0)
+    args = (p0, v0, sc.goal_d, 3, 10, 0.01, 64, 2, 1.0, 50.0)
+    kw = dict(seed=9, spheres=sc.sph_d, obstacle_weight=40.0, wind=sc.wind_d)
+    a = mcl.run_mppi(*args, log=True, **kw)
+    b = mcl.run_mppi_fused(*args, log=True, **kw)
+    for k in ("pos", "vel", "att", "omega", "time", "controller_state", "U", "cost", "trace", "clearance"):
+        assert bits_equal(a[k], b[k]), k
+    assert a["trace"].shape == (B, 3, 2) and len(a["logs"]) == 3 and len(b["logs"]) == 1
+    assert bits_equal(a["logs"][-1]["plan_last"], b["logs"][0]["plan_last"])
+    assert bits_equal(p0, sc.d(sc.p0)), "the caller's p0 is not modified"
+    hov = mcl.run_mppi_fused(*args, nominal=None, shift=N, **kw)["U"]
+    assert bits_equal(hov, torch.tensor([0.0, 0.0, sc.prm.mass * sc.prm.gravity], dtype=hov.dtype, device=hov.device).expand(B, N, 3)), "shift = N resets to hover"
+    c = mcl.run_mppi_fused(*args, seed=9)
+    assert c["clearance"] is None
+    st = sc.fresh()
+    with pytest.raises(ValueError):
+        h.ops.mppi_closed_loop(sc.prm, sc.cp, sc.sp, st["state"], st["time"], st["pos"], st["vel"], st["att"], st["omega"], sc.goal_d,
+                               st["U"][:, :N - 1].contiguous(), 1, 1, 0.01, 64, 1, 1.0, 1.0)

@@ -54,12 +54,6 @@ __device__ __forceinline__ R box_clip(const DevParams<R>& q, int a, R t) {
   return fmin(fmax(t, lo), hi);
 }
 
-__device__ __forceinline__ uint32_t orderable_cost_bits(float c) {        // the key order of se3mpc_argmin_*
-  const uint32_t u = __float_as_uint(c);
-  if (c != c) return 0xFFFFFFFEu;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 template <typename R>
 struct Ctx {
   DevParams<R> q;
@@ -275,7 +269,7 @@ __device__ __forceinline__ void write_nominal_cost(const Ctx<R>& c, int p, uint3
   const R cf = sample_cost<R, false>(c, 0u, (R)0);
   if ((threadIdx.x & (kWave - 1)) == 0) {
     cost_out[p] = cf;
-    if (keys != nullptr) keys[p] = ((uint64_t)orderable_cost_bits((float)cf) << 32) | (uint64_t)(index_base + (uint32_t)p);
+    if (keys != nullptr) keys[p] = ((uint64_t)orderable_bits((float)cf) << 32) | (uint64_t)(index_base + (uint32_t)p);
   }
 }
 

@@ -73,6 +73,16 @@ __device__ __forceinline__ void row_bounds(const DevParams<R>& q, int row, R& lo
   }
 }
 
+// Monotone map float -> uint32 (a < b  <=>  bits(a) < bits(b)) for the packed argmin keys.  NaN of either sign maps
+// to 0xFFFFFFFE: above every real cost (+inf is 0xFF800000), below the dead-lane sentinel 0xFFFFFFFF -- a diverged
+// trajectory can neither win the argmin (a negative NaN would otherwise sort below -inf) nor pass for a dead lane.
+// The one definition of the key order: every kernel that packs a key calls it, se3mpc_key_cost (api.hip) is its inverse.
+__device__ __forceinline__ uint32_t orderable_bits(float c) {
+  const uint32_t u = __float_as_uint(c);
+  if (c != c) return 0xFFFFFFFEu;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 // ---- host-side error plumbing -------------------------------------------------------------
 void set_last_error(const char* what, hipError_t e);
 void set_last_message(const char* what);   // an argument error (no HIP call involved)

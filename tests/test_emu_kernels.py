@@ -29,21 +29,21 @@ def harness(ops, dt):
 
 
 @pytest.mark.parametrize("dt", [np.float64, np.float32])
-@pytest.mark.parametrize("N,B", [(1, 5), (6, 70), (30, 66), (7, 9), (24, 65)])
+@pytest.mark.parametrize("N,B", [(1, 5), (6, 70), (30, 66), (7, 9), (24, 65), (16, 65), (17, 65), (32, 65), (33, 65)])
 def test_lane_kernels(emu_ops, dt, N, B):
     # B = 70 / 66 leave a partial last wavefront (tail lanes); N = 7 takes the generic (non-template) path
     pc.check_lane_kernels(harness(emu_ops, dt), N, B, seed=N, variants=(0, 1, 2, 3, 4, 5, 6))
 
 
 @pytest.mark.parametrize("dt", [np.float64, np.float32])
-@pytest.mark.parametrize("N,B", [(6, 70), (30, 66), (7, 9), (24, 65)])
+@pytest.mark.parametrize("N,B", [(6, 70), (30, 66), (7, 9), (24, 65), (16, 65), (17, 65), (32, 65), (33, 65)])
 def test_rollout_iterate(emu_ops, dt, N, B):
     # N = 6 / 30: exact-N register kernels (f64: 30 takes the through-memory path), 24: the 32-step bucket (f32), 7: through memory
     pc.check_rollout_iterate(harness(emu_ops, dt), N, B, seed=N, iters=4)
 
 
 @pytest.mark.parametrize("dt", [np.float64, np.float32])
-@pytest.mark.parametrize("N,B", [(6, 70), (30, 40), (7, 9), (24, 65)])
+@pytest.mark.parametrize("N,B", [(6, 70), (30, 40), (7, 9), (24, 65), (16, 65), (17, 65), (32, 65), (33, 65)])
 def test_rollout_iterate_obstacles(emu_ops, dt, N, B):
     # N = 6 / 30: exact-N register kernels (f64: 30 takes the through-memory path), 24: the 32-step bucket (f32), 7: through memory
     pc.check_rollout_iterate_obstacles(harness(emu_ops, dt), N, B, seed=N, iters=3)

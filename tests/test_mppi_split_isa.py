@@ -64,7 +64,7 @@ def test_split_kernels_keep_their_registers(isa):
 def test_the_device_code_is_shared_not_copied():
     """mppi.hip and mppi_split.hip take the sampler, the rollout and the weighted pass from csrc/mppi_device.hpp; neither defines them."""
     header = open(os.path.join(CSRC, "mppi_device.hpp")).read()
-    for name in ("philox4x32_10", "box_muller", "draw", "roll_step", "sample_cost", "box_clip", "orderable_cost_bits", "lds_layout", "weighted_pass"):
+    for name in ("philox4x32_10", "box_muller", "draw", "roll_step", "sample_cost", "box_clip", "orderable_bits", "lds_layout", "weighted_pass"):
         assert re.search(rf"\b{name}\(", header), name
         for f in ("mppi.hip", "mppi_split.hip"):
             src = open(os.path.join(CSRC, f)).read()

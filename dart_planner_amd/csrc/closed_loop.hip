@@ -185,13 +185,8 @@ closed_loop_kernel(CtrlDev<R> c, SimDev<R> m, int B, int nsteps, double sim_dt, 
     if (log_time != nullptr) log_time[(size_t)step * B + b] = t;
     R th = (R)NAN, tq[3] = {(R)NAN, (R)NAN, (R)NAN};
     if (active) {
-      R tp[3], tv[3], ta[3];
-      if (!(sim_dt > 0.0)) cur.idx = 0;                                        // a clock that does not advance: search from the start
-      sample_plan<R>(t, N, ts, Pb, Vb, Ab, tp, tv, ta, cur);
-      int fl;
-      control_step<R>(c, s, t, p, v, a, w, tp, tv, ta, (R)0, (R)0, th, tq, fl);
-      if (step == gust_step) { wd[0] = gx; wd[1] = gy; wd[2] = gz; }              // the gust of contract test :293-296
-      simulator_step<R>(m, p, v, a, w, t, th, tq, dt, sim_dt, wd);
+      if (step == gust_step) { wd[0] = gx; wd[1] = gy; wd[2] = gz; }              // the gust of contract test :293-296 (the controller does not see the wind)
+      flight_step<R>(c, m, s, cur, N, ts, Pb, Vb, Ab, p, v, a, w, t, dt, sim_dt, wd, th, tq);
       ++taken;
     }
     if (log_cmd != nullptr) {

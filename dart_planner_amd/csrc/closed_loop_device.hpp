@@ -1,5 +1,6 @@
 // closed_loop_device.hpp -- device code of the consumer side of the contract (plan sample -> geometric controller -> simulator step, one
-// drone per lane), shared by closed_loop.hip (its kernels and C entry points) and monte_carlo.hip (the fused receding-horizon loop).
+// drone per lane), shared by closed_loop.hip (its kernels and C entry points) and the fused receding-horizon loops of monte_carlo.hip and
+// mppi_closed_loop.hip (flight_step, fly_steps and the drone's LDS block).
 // INCLUDE UNDER `#pragma clang fp contract(off)`: the controller's saturation / singularity / failsafe branches compare against values
 // NumPy computes without FMA (see closed_loop.hip).
 #pragma once
@@ -377,6 +378,90 @@ __device__ __forceinline__ void simulator_step(const SimDev<R>& m, R pos[3], R v
     att[i] = att[i] + omega[i] * dt;                                              // :65
   }
   t = t + dt_d;                                                                   // :67
+}
+
+// One flight step of one drone: the plan sampled at the drone's clock (a clock that does not advance searches from the start), the
+// geometric controller on the sample with yaw = yaw rate = 0, the simulator step under the command.  -> the command (th, tq).
+// The step of se3mpc_closed_loop_*, se3mpc_monte_carlo_* and se3mpc_mppi_closed_loop_*: one definition, hence the same bits.
+template <typename R>
+__device__ __forceinline__ void flight_step(const CtrlDev<R>& c, const SimDev<R>& m, CtrlRegs<R>& s, PlanCursor<R>& cur, int N,
+                                            const double* ts, const R* P, const R* V, const R* A, R p[3], R v[3], R a[3], R w[3], double& t,
+                                            R dt, double sim_dt, const R wd[3], R& th, R tq[3]) {
+  R tp[3], tv[3], ta[3];
+  if (!(sim_dt > 0.0)) cur.idx = 0;
+  sample_plan<R>(t, N, ts, P, V, A, tp, tv, ta, cur);
+  int fl;
+  control_step<R>(c, s, t, p, v, a, w, tp, tv, ta, (R)0, (R)0, th, tq, fl);
+  simulator_step<R>(m, p, v, a, w, t, th, tq, dt, sim_dt, wd);
+}
+
+// A drone of the fused receding-horizon kernels, parked in LDS while the planner has the registers: the plan the planner hands over
+// (n rows of P, V, A and their stamps), the drone's clock, its controller record and vec = pos, vel, att, omega, wind [15] (a kernel
+// may keep values of its own behind them).
+template <typename R>
+struct DroneBlock {
+  double* stamps;   // [n]
+  double* time;     // [1]
+  double* ctrl;     // [SE3MPC_CONTROLLER_STATE_WORDS]
+  R *planP, *planV, *planA;   // [n][3] each
+  R* vec;
+};
+// stamps, time and the controller record lie at `base`, the three plans from byte `plan_off`, vec at byte `vec_off`
+template <typename R>
+__device__ __forceinline__ DroneBlock<R> drone_block(unsigned char* base, int n, size_t plan_off, size_t vec_off) {
+  DroneBlock<R> d;
+  d.stamps = reinterpret_cast<double*>(base);
+  d.time = d.stamps + n;
+  d.ctrl = d.time + 1;
+  d.planP = reinterpret_cast<R*>(base + plan_off);
+  d.planV = d.planP + 3 * n;
+  d.planA = d.planV + 3 * n;
+  d.vec = reinterpret_cast<R*>(base + vec_off);
+  return d;
+}
+
+// Drone b of the [B][3] state arrays, the clocks and the controller records into its block (wind: null = none) ...
+template <typename R>
+__device__ __forceinline__ void drone_load(const DroneBlock<R>& d, int b, const R* __restrict__ posg, const R* __restrict__ velg,
+                                           const R* __restrict__ attg, const R* __restrict__ omegag, const R* __restrict__ windg,
+                                           long long wind_stride, const double* __restrict__ timeg, const double* __restrict__ stateg) {
+  for (int i = 0; i < 3; ++i) {
+    d.vec[i] = posg[3 * b + i]; d.vec[3 + i] = velg[3 * b + i]; d.vec[6 + i] = attg[3 * b + i]; d.vec[9 + i] = omegag[3 * b + i];
+    d.vec[12 + i] = windg != nullptr ? windg[(size_t)b * wind_stride + i] : (R)0;
+  }
+  *d.time = timeg[b];
+  for (int i = 0; i < SE3MPC_CONTROLLER_STATE_WORDS; ++i) d.ctrl[i] = stateg[(size_t)b * SE3MPC_CONTROLLER_STATE_WORDS + i];
+}
+// ... and back
+template <typename R>
+__device__ __forceinline__ void drone_store(const DroneBlock<R>& d, int b, R* __restrict__ posg, R* __restrict__ velg, R* __restrict__ attg,
+                                            R* __restrict__ omegag, double* __restrict__ timeg, double* __restrict__ stateg) {
+  for (int i = 0; i < 3; ++i) { posg[3 * b + i] = d.vec[i]; velg[3 * b + i] = d.vec[3 + i]; attg[3 * b + i] = d.vec[6 + i]; omegag[3 * b + i] = d.vec[9 + i]; }
+  timeg[b] = *d.time;
+  for (int i = 0; i < SE3MPC_CONTROLLER_STATE_WORDS; ++i) stateg[(size_t)b * SE3MPC_CONTROLLER_STATE_WORDS + i] = d.ctrl[i];
+}
+
+// `n` flight steps of the drone in block d against its N-row plan, by ONE lane: state and controller record from LDS into registers,
+// the steps, and back.  after_step(step, pos) is called behind every step.  c and m by value: a copy of its own that the loop reads, not
+// the caller's kernel arguments (measured on se3mpc_mppi_closed_loop_f64: by reference the loop is 3 % slower).
+template <typename R, typename F>
+__device__ __forceinline__ void fly_steps(const CtrlDev<R> c, const SimDev<R> m, const DroneBlock<R>& d, int N, int n, double sim_dt,
+                                          F&& after_step) {
+  CtrlRegs<R> s = load_ctrl<R>(d.ctrl);
+  R p[3], v[3], a[3], w[3], wd[3];
+  for (int i = 0; i < 3; ++i) { p[i] = d.vec[i]; v[i] = d.vec[3 + i]; a[i] = d.vec[6 + i]; w[i] = d.vec[9 + i]; wd[i] = d.vec[12 + i]; }
+  double t = *d.time;
+  const R dt = (R)sim_dt;
+  PlanCursor<R> cur;
+  cursor_reset(cur);
+  for (int step = 0; step < n; ++step) {
+    R th, tq[3];
+    flight_step<R>(c, m, s, cur, N, d.stamps, d.planP, d.planV, d.planA, p, v, a, w, t, dt, sim_dt, wd, th, tq);
+    after_step(step, p);
+  }
+  for (int i = 0; i < 3; ++i) { d.vec[i] = p[i]; d.vec[3 + i] = v[i]; d.vec[6 + i] = a[i]; d.vec[9 + i] = w[i]; }
+  *d.time = t;
+  store_ctrl<R>(d.ctrl, s);
 }
 
 static inline int check_controller_params(const se3mpc_controller_params* p) {

@@ -2,7 +2,8 @@
 // (/root/reference/tests/test_monte_carlo_sim.py:24-72: `cycles` planning cycles of `substeps` control + simulator steps per drone) in
 // ONE launch: every planning cycle of every drone runs inside the same kernel -- solve (solve_body.inc, the batched solver's own
 // code: same bits as se3mpc_solve_*), plan handed to the controller through LDS, `substeps` x (plan sample -> geometric controller ->
-// simulator step) (closed_loop_device.hpp, the closed-loop kernel's own code: same bits as se3mpc_closed_loop_*), next cycle.
+// simulator step) (fly_steps of closed_loop_device.hpp, around the closed-loop kernel's own flight_step: same bits as
+// se3mpc_closed_loop_*), next cycle.
 //
 // Why: driven as 2 x cycles launches (se3mpc_solve_* + se3mpc_closed_loop_* per cycle, control/closed_loop.py) every cycle waits at two
 // kernel boundaries for its SLOWEST drone.  In the loop's own statistics 99.4 % of the solves stop after one L-BFGS-B iteration and a
@@ -19,13 +20,32 @@
 
 namespace se3mpc {
 
-// LDS of one wavefront behind the solver's image: per drone (group) the plan [3][G][3] in the IO type (positions, velocities,
-// accelerations as the solver stores them), its G stamps, and the drone's state: pos, vel, att, omega, wind (15 IO), time (1 double),
-// controller record (SE3MPC_CONTROLLER_STATE_WORDS doubles)
+// LDS of one wavefront behind the solver's image: per drone (group) a DroneBlock with G plan rows in the IO type (positions, velocities,
+// accelerations as the solver stores them) -- G stamps, time, controller record (doubles), the plan [3][G][3], then pos, vel, att,
+// omega, wind (15 IO) -- and behind it, 16-byte aligned, the controller's and the simulator's constants: parked in LDS too, so that
+// the ~50 scalar registers they would occupy as kernel arguments are free while the solver runs (read back inside the act phase only)
 template <typename IO>
-__host__ __device__ constexpr size_t mc_group_bytes(int G) {
-  return ((size_t)(9 * G + 16) * sizeof(IO) + (size_t)(G + 1 + SE3MPC_CONTROLLER_STATE_WORDS) * sizeof(double) + 15) / 16 * 16 +
-         (sizeof(CtrlDev<IO>) + sizeof(SimDev<IO>) + 15) / 16 * 16;
+__host__ __device__ constexpr size_t mc_plan_offset(int G) { return (size_t)(G + 1 + SE3MPC_CONTROLLER_STATE_WORDS) * sizeof(double); }
+template <typename IO>
+__host__ __device__ constexpr size_t mc_consts_offset(int G) { return (mc_plan_offset<IO>(G) + (size_t)(9 * G + 16) * sizeof(IO) + 15) / 16 * 16; }
+template <typename IO>
+__host__ __device__ constexpr size_t mc_group_bytes(int G) { return mc_consts_offset<IO>(G) + (sizeof(CtrlDev<IO>) + sizeof(SimDev<IO>) + 15) / 16 * 16; }
+
+template <typename IO>
+struct McBlock {
+  DroneBlock<IO> d;
+  CtrlDev<IO>* ctl;
+  SimDev<IO>* sim;
+};
+// Group grp's block.  Built again inside each phase: only `grp` stays live while the solver has the registers.
+template <typename IO, int G>
+__device__ __forceinline__ McBlock<IO> mc_block(unsigned char* lds_raw, size_t solver_lds, int grp) {
+  unsigned char* gb = lds_raw + solver_lds + (size_t)grp * mc_group_bytes<IO>(G);
+  McBlock<IO> b;
+  b.d = drone_block<IO>(gb, G, mc_plan_offset<IO>(G), mc_plan_offset<IO>(G) + (size_t)9 * G * sizeof(IO));
+  b.ctl = reinterpret_cast<CtrlDev<IO>*>(gb + mc_consts_offset<IO>(G));
+  b.sim = reinterpret_cast<SimDev<IO>*>(b.ctl + 1);
+  return b;
 }
 
 // One wavefront per SIMD (512 registers): the kernel is a chain of dependent scalar recurrences -- a second resident wavefront would
@@ -48,35 +68,15 @@ monte_carlo_kernel(SolveDev q, CtrlDev<IO> ctl, SimDev<IO> sim, int B, int cycle
   const int grp = lane / G;
   const int pb = blockIdx.x * P + grp;     // drone index
   if (pb >= B) return;                     // (a whole group leaves together)
-  // ---- this drone's LDS block (pointers are re-derived inside each phase: only `grp` stays live while the solver has the registers)
-#define SE3MPC_MC_BLOCK()                                                                                                              \
-  unsigned char* gb = lds_raw + solver_lds + (size_t)grp * mc_group_bytes<IO>(G);                                                       \
-  double* stamps = reinterpret_cast<double*>(gb);                                  /* [G] */                                            \
-  double* s_time = stamps + G;                                                     /* [1] */                                            \
-  double* s_ctrl = s_time + 1;                                                     /* [SE3MPC_CONTROLLER_STATE_WORDS] */                \
-  IO* planP = reinterpret_cast<IO*>(s_ctrl + SE3MPC_CONTROLLER_STATE_WORDS);       /* [G][3] */                                         \
-  IO* planV = planP + 3 * G;                                                                                                            \
-  IO* planA = planV + 3 * G;                                                                                                            \
-  IO* s_vec = planA + 3 * G;                                                       /* pos, vel, att, omega, wind: [15] */               \
-  /* the controller's and the simulator's constants: parked in LDS too, so that the ~50 scalar registers they would occupy as kernel */ \
-  /* arguments are free while the solver runs (they are read back inside the act phase only) */                                        \
-  CtrlDev<IO>* l_ctl = reinterpret_cast<CtrlDev<IO>*>(gb + ((size_t)(9 * G + 16) * sizeof(IO) + (size_t)(G + 1 + SE3MPC_CONTROLLER_STATE_WORDS) * sizeof(double) + 15) / 16 * 16); \
-  SimDev<IO>* l_sim = reinterpret_cast<SimDev<IO>*>(l_ctl + 1);                                                                         \
-  (void)stamps; (void)s_time; (void)s_ctrl; (void)planP; (void)planV; (void)planA; (void)s_vec; (void)l_ctl; (void)l_sim;
   double goal[3] = {0.0, 0.0, 0.0};
   if (q.has_goal) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) goal[a] = (double)goalg[pb * 3 + a];
   }
   if (k == 0) {
-    SE3MPC_MC_BLOCK()
-    for (int i = 0; i < 3; ++i) {
-      s_vec[i] = posg[3 * pb + i]; s_vec[3 + i] = velg[3 * pb + i]; s_vec[6 + i] = attg[3 * pb + i]; s_vec[9 + i] = omegag[3 * pb + i];
-      s_vec[12 + i] = windg != nullptr ? windg[(size_t)pb * wind_stride + i] : (IO)0;
-    }
-    *s_time = timeg[pb];
-    *l_ctl = ctl; *l_sim = sim;
-    for (int i = 0; i < SE3MPC_CONTROLLER_STATE_WORDS; ++i) s_ctrl[i] = stateg[(size_t)pb * SE3MPC_CONTROLLER_STATE_WORDS + i];
+    const McBlock<IO> blk = mc_block<IO, G>(lds_raw, solver_lds, grp);
+    *blk.ctl = ctl; *blk.sim = sim;
+    drone_load<IO>(blk.d, pb, posg, velg, attg, omegag, windg, wind_stride, timeg, stateg);
   }
   group_sync<G>();
   const IO* x0row = nullptr;               // every cycle re-plans from the reference's cold start
@@ -85,7 +85,7 @@ monte_carlo_kernel(SolveDev q, CtrlDev<IO> ctl, SimDev<IO> sim, int B, int cycle
     // ---- plan: the batched solver's body on (pos, vel) as the solve kernel would read them from its [B][3] arrays
     double ps[3], vs[3];
     {
-      SE3MPC_MC_BLOCK()
+      const IO* s_vec = mc_block<IO, G>(lds_raw, solver_lds, grp).d.vec;
 #pragma unroll
       for (int a = 0; a < 3; ++a) { ps[a] = (double)s_vec[a]; vs[a] = (double)s_vec[3 + a]; }
     }
@@ -93,13 +93,13 @@ monte_carlo_kernel(SolveDev q, CtrlDev<IO> ctl, SimDev<IO> sim, int B, int cycle
     {
 #include "solve_body.inc"
       if (task == SE3MPC_TASK_OVERFLOW && k == 0) atomicAdd(overflowed, 1);      // the LDS image was too small for this solve: the caller falls back
-      SE3MPC_MC_BLOCK()
+      const DroneBlock<IO> drone = mc_block<IO, G>(lds_raw, solver_lds, grp).d;
       // the plan as se3mpc_solve_* stores it (rounded to the IO type) and as se3mpc_closed_loop_* reads it
       if (live) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { planP[3 * k + a] = (IO)x[a]; planV[3 * k + a] = (IO)x[3 + a]; }
-        planA[3 * k + 0] = (IO)(x[6] / q.mass); planA[3 * k + 1] = (IO)(x[7] / q.mass); planA[3 * k + 2] = (IO)(x[8] / q.mass - q.grav);
-        stamps[k] = plan_stamp(cycle, substeps, sim_dt, k, q.dt);
+        for (int a = 0; a < 3; ++a) { drone.planP[3 * k + a] = (IO)x[a]; drone.planV[3 * k + a] = (IO)x[3 + a]; }
+        drone.planA[3 * k + 0] = (IO)(x[6] / q.mass); drone.planA[3 * k + 1] = (IO)(x[7] / q.mass); drone.planA[3 * k + 2] = (IO)(x[8] / q.mass - q.grav);
+        drone.stamps[k] = plan_stamp(cycle, substeps, sim_dt, k, q.dt);
       }
       if (cycle == cycles - 1 && live) {
         if (Xg != nullptr) {
@@ -108,7 +108,7 @@ monte_carlo_kernel(SolveDev q, CtrlDev<IO> ctl, SimDev<IO> sim, int B, int cycle
         }
         if (accg != nullptr) {
           const size_t o = (size_t)pb * n3 + 3 * k;
-          accg[o] = planA[3 * k + 0]; accg[o + 1] = planA[3 * k + 1]; accg[o + 2] = planA[3 * k + 2];
+          accg[o] = drone.planA[3 * k + 0]; accg[o + 1] = drone.planA[3 * k + 1]; accg[o + 2] = drone.planA[3 * k + 2];
         }
         if (infog != nullptr && k == 0) {
           se3mpc_solve_info r;
@@ -118,40 +118,16 @@ monte_carlo_kernel(SolveDev q, CtrlDev<IO> ctl, SimDev<IO> sim, int B, int cycle
       }
     }
     group_sync<G>();
-    // ---- act: `substeps` x (sample the plan, geometric controller, simulator step) on the group's first lane
+    // ---- act: `substeps` flight steps (closed_loop_device.hpp: sample the plan, geometric controller, simulator step) on the group's first lane
     if (k == 0) {
-      SE3MPC_MC_BLOCK()
-      const CtrlDev<IO> c = *l_ctl;
-      const SimDev<IO> m = *l_sim;
-      CtrlRegs<IO> s = load_ctrl<IO>(s_ctrl);
-      IO p[3], v[3], a[3], w[3], wd[3];
-      for (int i = 0; i < 3; ++i) { p[i] = s_vec[i]; v[i] = s_vec[3 + i]; a[i] = s_vec[6 + i]; w[i] = s_vec[9 + i]; wd[i] = s_vec[12 + i]; }
-      double t = *s_time;
-      const IO dt = (IO)sim_dt;
-      PlanCursor<IO> cur;
-      cursor_reset(cur);
-      for (int step = 0; step < substeps; ++step) {
-        IO tp[3], tv[3], ta[3];
-        if (!(sim_dt > 0.0)) cur.idx = 0;
-        sample_plan<IO>(t, q.N, stamps, planP, planV, planA, tp, tv, ta, cur);
-        IO th, tq[3];
-        int fl;
-        control_step<IO>(c, s, t, p, v, a, w, tp, tv, ta, (IO)0, (IO)0, th, tq, fl);
-        simulator_step<IO>(m, p, v, a, w, t, th, tq, dt, sim_dt, wd);
-      }
-      for (int i = 0; i < 3; ++i) { s_vec[i] = p[i]; s_vec[3 + i] = v[i]; s_vec[6 + i] = a[i]; s_vec[9 + i] = w[i]; }
-      *s_time = t;
-      store_ctrl<IO>(s_ctrl, s);
+      const McBlock<IO> blk = mc_block<IO, G>(lds_raw, solver_lds, grp);
+      const CtrlDev<IO> c = *blk.ctl;
+      const SimDev<IO> m = *blk.sim;
+      fly_steps<IO>(c, m, blk.d, q.N, substeps, sim_dt, [](int, const IO*) {});
     }
     group_sync<G>();
   }
-  if (k == 0) {
-    SE3MPC_MC_BLOCK()
-    for (int i = 0; i < 3; ++i) { posg[3 * pb + i] = s_vec[i]; velg[3 * pb + i] = s_vec[3 + i]; attg[3 * pb + i] = s_vec[6 + i]; omegag[3 * pb + i] = s_vec[9 + i]; }
-    timeg[pb] = *s_time;
-    for (int i = 0; i < SE3MPC_CONTROLLER_STATE_WORDS; ++i) stateg[(size_t)pb * SE3MPC_CONTROLLER_STATE_WORDS + i] = s_ctrl[i];
-  }
-#undef SE3MPC_MC_BLOCK
+  if (k == 0) drone_store<IO>(mc_block<IO, G>(lds_raw, solver_lds, grp).d, pb, posg, velg, attg, omegag, timeg, stateg);
 }
 
 template <typename IO>
@@ -174,7 +150,7 @@ int monte_carlo_impl(const se3mpc_params* p, const se3mpc_controller_params* cp,
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(overflowed, 0, sizeof(int32_t), s) != hipSuccess) return launch_status("se3mpc_monte_carlo(memset)");
   SolveDev q = make_solve_dev(*p);
-  const int G = p->horizon <= 8 ? 8 : (p->horizon <= 16 ? 16 : (p->horizon <= 32 ? 32 : 64));
+  const int G = solve_group_for_horizon(p->horizon);
   const int waves = (int)(((long)B * G + kWave - 1) / kWave);
   // pairs of L-BFGS memory the LDS image holds: as many (<= maxcor) as still let every wavefront of the launch be resident at once,
   // at least 4 -- a solve with the reference's options stores at most two; a solve that needs more raises `overflowed`
@@ -188,19 +164,13 @@ int monte_carlo_impl(const se3mpc_params* p, const se3mpc_controller_params* cp,
   const size_t lds = solver_lds + extra;
   const CtrlDev<IO> c = make_ctrl_dev<IO>(*cp);
   const SimDev<IO> m = make_sim_dev<IO>(*sp);
-#define SE3MPC_MC_CASE(GG)                                                                                                       \
-  {                                                                                                                              \
-    if (lds > 64 * 1024)                                                                                                         \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&monte_carlo_kernel<IO, GG>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds);                                                                                       \
-    hipLaunchKernelGGL((monte_carlo_kernel<IO, GG>), dim3(waves), dim3(kWave), lds, s, q, c, m, B, cycles, substeps, sim_dt, solver_lds, \
-                       goal, wind, wind_stride, time, pos, vel, att, omega, state, X_last, acc_last, info_last, overflowed);    \
-  }
-  if (G == 8) SE3MPC_MC_CASE(8)
-  else if (G == 16) SE3MPC_MC_CASE(16)
-  else if (G == 32) SE3MPC_MC_CASE(32)
-  else SE3MPC_MC_CASE(64)
-#undef SE3MPC_MC_CASE
+  dispatch_group(G, [&](auto g) {
+    constexpr int GG = decltype(g)::value;
+    if (lds > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&monte_carlo_kernel<IO, GG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((monte_carlo_kernel<IO, GG>), dim3(waves), dim3(kWave), lds, s, q, c, m, B, cycles, substeps, sim_dt, solver_lds, goal,
+                       wind, wind_stride, time, pos, vel, att, omega, state, X_last, acc_last, info_last, overflowed);
+  });
   return launch_status("se3mpc_monte_carlo");
 }
 

@@ -28,26 +28,17 @@ mppi_kernel(DevParams<R> q, int ld, int S, int iters, R sigma, double inv_lam, u
   const int N = q.N, rows = 3 * N, NT = (int)blockDim.x, W = NT / kWave;
   const int tid = (int)threadIdx.x, wave = tid / kWave;
   const int p = (int)blockIdx.x;
-  const Lds L = lds_layout(N, K, W, sizeof(R));
-  double* acc = reinterpret_cast<double*>(lds_raw + L.acc);
-  double* part = reinterpret_cast<double*>(lds_raw + L.part);
-  double* red = reinterpret_cast<double*>(lds_raw + L.red);
-  R* U = reinterpret_cast<R*>(lds_raw + L.U);
-  R* sph = reinterpret_cast<R*>(lds_raw + L.sph);
+  const LdsView<R> l = lds_view<R>(lds_raw, lds_layout(N, K, W, sizeof(R)));
+  R* U = l.U;
   for (int r = tid; r < rows; r += NT) U[r] = U_in[(size_t)r * ld + p];
-  stage_spheres(q, spheres, K, sph);
-  Ctx<R> c = load_ctx(q, ld, p, key0, key1, index_base + (uint32_t)p, p0, v0, goal, U, sph, K, w_obs);
+  stage_spheres(q, spheres, K, l.sph);
+  Ctx<R> c = load_ctx(q, ld, p, key0, key1, index_base + (uint32_t)p, p0, v0, goal, U, l.sph, K, w_obs);
   const uint32_t g0 = iter_base + (iter_offset != nullptr ? *iter_offset : 0u);
   __syncthreads();
   for (int it = 0; it < iters; ++it) {
     c.g = g0 + (uint32_t)it;
-    const double m = weighted_pass<R>(c, U, 0, S, sigma, inv_lam, acc, part, red);
-    // U <- weighted mean (the clip only guards the rounding of the division: a mean of in-box samples is in the box)
-    const double wsum = acc[rows];
-    for (int r = tid; r < rows; r += NT)
-      if (wsum > 0.0) U[r] = box_clip(q, r % 3, (R)(acc[r] / wsum));
-    if (tid == 0 && trace != nullptr) trace[(size_t)it * ld + p] = (R)m;
-    __syncthreads();
+    const double m = weighted_pass<R>(c, U, 0, S, sigma, inv_lam, l.acc, l.part, l.red);
+    nominal_update(q, l.acc, U, m, trace, (size_t)it * ld + p);
   }
   if (wave == 0) write_nominal_cost(c, p, index_base, cost_out, keys);
   for (int r = tid; r < rows; r += NT) U_out[(size_t)r * ld + p] = U[r];
@@ -81,33 +72,13 @@ mppi_samples_kernel(DevParams<R> q, int nprob, int ld, int S, R sigma, uint32_t 
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-static int fail(int rc, const char* what) {
-  set_last_message(what);
-  return rc;
-}
-
-static int check_common(const se3mpc_params* p, int nprob, int ld, int S, double sigma, const char* fn) {
-  if (p == nullptr) return fail(SE3MPC_ERR_NULL, fn);
-  const int rc = check_params_impl(p);
-  if (rc != SE3MPC_OK) return fail(rc, fn);
-  if (nprob < 0 || ld < nprob) return fail(SE3MPC_ERR_SHAPE, fn);
-  if (S < kMinS || S > kMaxS || S % kWave != 0) return fail(SE3MPC_ERR_SHAPE, fn);
-  if (!(sigma >= 0.0) || !std::isfinite(sigma)) return fail(SE3MPC_ERR_PARAM, fn);
-  return SE3MPC_OK;
-}
-
 template <typename R>
 static int mppi_impl(const se3mpc_params* p, int nprob, int ld, int S, int iters, double sigma, double temperature, uint64_t seed,
                      uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const R* p0, const R* v0, const R* goal,
                      const R* U_in, R* U_out, const R* spheres, int K, double obstacle_weight, R* cost, R* trace, uint64_t* keys,
                      void* stream) {
-  static const char* fn = "se3mpc_mppi: invalid argument";
-  int rc = check_common(p, nprob, ld, S, sigma, fn);
+  const int rc = check_mppi_args("se3mpc_mppi", p, nprob, ld, S, iters, sigma, temperature, K, obstacle_weight);
   if (rc) return rc;
-  if (iters < 0) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi: iters < 0");
-  if (K < 0 || K > SE3MPC_MAX_SPHERES) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi: K outside [0, SE3MPC_MAX_SPHERES]");
-  if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(SE3MPC_ERR_PARAM, "se3mpc_mppi: temperature must be finite and > 0");
-  if (!(obstacle_weight >= 0.0) || !std::isfinite(obstacle_weight)) return fail(SE3MPC_ERR_PARAM, "se3mpc_mppi: obstacle_weight must be finite and >= 0");
   if (nprob == 0) return SE3MPC_OK;
   if (!p0 || !v0 || (p->has_goal && !goal) || !U_in || !U_out || !cost || (K > 0 && !spheres)) return fail(SE3MPC_ERR_NULL, "se3mpc_mppi: NULL operand");
   const int NT = S < kBlock ? S : kBlock;
@@ -123,8 +94,7 @@ static int mppi_impl(const se3mpc_params* p, int nprob, int ld, int S, int iters
 template <typename R>
 static int mppi_samples_impl(const se3mpc_params* p, int nprob, int ld, int S, double sigma, uint64_t seed, uint32_t iter_base,
                              uint32_t index_base, const R* U_in, R* T_out, int ld_out, R* noise, uint32_t* raw, void* stream) {
-  static const char* fn = "se3mpc_mppi_samples: invalid argument";
-  int rc = check_common(p, nprob, ld, S, sigma, fn);
+  const int rc = check_mppi_batch("se3mpc_mppi_samples", p, nprob, ld, S, sigma);
   if (rc) return rc;
   if ((long long)S * nprob > (long long)ld_out || (long long)S * nprob > 0x7FFFFFFFLL) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_samples: ld_out < S * nprob");
   if (nprob == 0) return SE3MPC_OK;

@@ -1,11 +1,11 @@
 // mppi_closed_loop.hip -- the receding-horizon closed-loop Monte-Carlo whose planner is MPPI, every drone and every planning cycle in ONE
 // launch.  One workgroup of min(S, 256) lanes per drone; cycle c (C = cycle_base + c) of drone b (q = index_base + b):
-//   plan       `iters` MPPI iterations from the drone's own (pos, vel) on its nominal U: weighted_pass and the update of mppi.hip, the same
-//              code in the same order, hence the same bits as se3mpc_mppi_*; iteration number g = iter_base + C * iters + i
+//   plan       `iters` MPPI iterations from the drone's own (pos, vel) on its nominal U: weighted_pass and nominal_update of mppi_device.hpp,
+//              the functions mppi_kernel calls, hence the same bits as se3mpc_mppi_*; iteration number g = iter_base + C * iters + i
 //   hand over  the updated nominal rolled out with roll_step's recurrence into LDS: row k = the state BEFORE step k, A_k the acceleration of
 //              U_k, stamped plan_stamp(C, substeps, sim_dt, k, dt).  The plan never reaches HBM (plan_last in the last cycle excepted)
-//   act        `substeps` x (sample_plan -> control_step -> simulator_step) on the workgroup's first lane: the loop of closed_loop.hip
-//              with yaw 0, no gust and no stop at the plan's end (closed_loop_device.hpp, the same code, hence the same bits)
+//   act        `substeps` x flight_step (sample_plan -> control_step with yaw 0 -> simulator_step) on the workgroup's first lane: fly_steps of
+//              closed_loop_device.hpp, around the step closed_loop_kernel itself calls (no gust, no stop at the plan's end), hence the same bits
 //   clearance  the positions the simulator produced are parked in LDS and the whole workgroup reduces min_j(|pos - c_j| - r_j) over them
 //   warm start U[k] <- U[k + shift], hover behind
 // The drone's state, its controller record, the plan and its stamps live in LDS behind the image of lds_layout.  No atomics, no
@@ -22,7 +22,7 @@ constexpr int kPark = 64;     // simulator positions parked per clearance reduct
 
 // Wavefronts per SIMD the kernel is compiled for, chosen from the ISA.  The act phase holds the geometric controller in
 // one lane's registers: at the planner's four wavefronts per SIMD (128 registers) the float kernel spills 9 registers and the double
-// kernel far more.  Without spills the float kernel needs 144 registers (three wavefronts) and the double kernel 233 (two).
+// kernel far more.  Without spills the float kernel needs 139 registers (three wavefronts) and the double kernel 234 (two).
 template <typename R>
 struct LoopWaves { static constexpr int value = 3; };
 template <>
@@ -59,20 +59,12 @@ mppi_closed_loop_kernel(DevParams<R> q, CtrlDev<R> ctl, SimDev<R> sim, double pl
   const int N = q.N, rows = 3 * N, NT = (int)blockDim.x, W = NT / kWave;
   const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const int b = (int)blockIdx.x;
-  const Lds L = lds_layout(N, K, W, sizeof(R));
   const LoopLds X = loop_lds_layout(N, K, W, sizeof(R));
-  double* acc = reinterpret_cast<double*>(lds_raw + L.acc);
-  double* part = reinterpret_cast<double*>(lds_raw + L.part);
-  double* red = reinterpret_cast<double*>(lds_raw + L.red);
-  R* U = reinterpret_cast<R*>(lds_raw + L.U);
-  R* sph = reinterpret_cast<R*>(lds_raw + L.sph);
-  double* stamps = reinterpret_cast<double*>(lds_raw + X.stamps);
-  double* s_time = reinterpret_cast<double*>(lds_raw + X.time);
-  double* s_ctrl = reinterpret_cast<double*>(lds_raw + X.ctrl);
-  R* planP = reinterpret_cast<R*>(lds_raw + X.plan);
-  R* planV = planP + rows;
-  R* planA = planV + rows;
-  R* s_vec = reinterpret_cast<R*>(lds_raw + X.vec);        // pos, vel, att, omega, wind, goal, running clearance
+  const LdsView<R> l = lds_view<R>(lds_raw, lds_layout(N, K, W, sizeof(R)));
+  R* U = l.U;
+  R* sph = l.sph;
+  const DroneBlock<R> d = drone_block<R>(lds_raw + X.stamps, N, X.plan - X.stamps, X.vec - X.stamps);
+  R* s_vec = d.vec;                                         // pos, vel, att, omega, wind | goal, running clearance
   R* rad = reinterpret_cast<R*>(lds_raw + X.rad);
   R* park = reinterpret_cast<R*>(lds_raw + X.park);
   const bool want_clear = clearance != nullptr && K > 0;
@@ -81,14 +73,9 @@ mppi_closed_loop_kernel(DevParams<R> q, CtrlDev<R> ctl, SimDev<R> sim, double pl
   stage_spheres(q, spheres, K, sph);
   for (int j = tid; j < K; j += NT) rad[j] = spheres[4 * j + 3];
   if (tid == 0) {
-    for (int i = 0; i < 3; ++i) {
-      s_vec[i] = posg[3 * b + i]; s_vec[3 + i] = velg[3 * b + i]; s_vec[6 + i] = attg[3 * b + i]; s_vec[9 + i] = omegag[3 * b + i];
-      s_vec[12 + i] = windg != nullptr ? windg[(size_t)b * wind_stride + i] : (R)0;
-      s_vec[15 + i] = q.has_goal ? goalg[3 * b + i] : (R)0;
-    }
+    drone_load<R>(d, b, posg, velg, attg, omegag, windg, wind_stride, timeg, stateg);
+    for (int i = 0; i < 3; ++i) s_vec[15 + i] = q.has_goal ? goalg[3 * b + i] : (R)0;
     s_vec[18] = want_clear ? clearance[b] : (R)0;
-    *s_time = timeg[b];
-    for (int i = 0; i < SE3MPC_CONTROLLER_STATE_WORDS; ++i) s_ctrl[i] = stateg[(size_t)b * SE3MPC_CONTROLLER_STATE_WORDS + i];
   }
   __syncthreads();
   // the planner's context as mppi_kernel builds it (load_ctx), from the LDS copies of the state and the goal
@@ -107,12 +94,8 @@ mppi_closed_loop_kernel(DevParams<R> q, CtrlDev<R> ctl, SimDev<R> sim, double pl
     const uint32_t g0 = iter_base + C * (uint32_t)iters;
     for (int it = 0; it < iters; ++it) {
       c.g = g0 + (uint32_t)it;
-      const double m = weighted_pass<R>(c, U, 0, S, sigma, inv_lam, acc, part, red);
-      const double wsum = acc[rows];
-      for (int r = tid; r < rows; r += NT)
-        if (wsum > 0.0) U[r] = box_clip(q, r % 3, (R)(acc[r] / wsum));
-      if (tid == 0 && trace != nullptr) trace[((size_t)b * cycles + cyc) * iters + it] = (R)m;
-      __syncthreads();
+      const double m = weighted_pass<R>(c, U, 0, S, sigma, inv_lam, l.acc, l.part, l.red);
+      nominal_update(q, l.acc, U, m, trace, ((size_t)b * cycles + cyc) * iters + it);
     }
     if (last && wave == 0) write_nominal_cost(c, b, index_base, cost_out, (uint64_t*)nullptr);
     // ---- hand over: the nominal's trajectory, row k = the state before step k
@@ -121,38 +104,20 @@ mppi_closed_loop_kernel(DevParams<R> q, CtrlDev<R> ctl, SimDev<R> sim, double pl
       for (int k = 0; k < N; ++k) {
         R a3[3];
         const R t[3] = {U[3 * k], U[3 * k + 1], U[3 * k + 2]};
-        for (int a = 0; a < 3; ++a) { planP[3 * k + a] = p[a]; planV[3 * k + a] = v[a]; }
+        for (int a = 0; a < 3; ++a) { d.planP[3 * k + a] = p[a]; d.planV[3 * k + a] = v[a]; }
         roll_state_step(q, p, v, t, a3);
-        for (int a = 0; a < 3; ++a) planA[3 * k + a] = a3[a];
-        stamps[k] = plan_stamp((int)C, substeps, sim_dt, k, plan_dt);
+        for (int a = 0; a < 3; ++a) d.planA[3 * k + a] = a3[a];
+        d.stamps[k] = plan_stamp((int)C, substeps, sim_dt, k, plan_dt);
       }
     }
     // ---- act, in chunks of kPark steps: the first lane flies, then the workgroup measures the clearance of the positions it left
     int s0 = 0;
     do {
       const int n = substeps - s0 < kPark ? substeps - s0 : kPark;
-      if (tid == 0 && n > 0) {
-        CtrlRegs<R> s = load_ctrl<R>(s_ctrl);
-        R p[3], v[3], a[3], w[3], wd[3];
-        for (int i = 0; i < 3; ++i) { p[i] = s_vec[i]; v[i] = s_vec[3 + i]; a[i] = s_vec[6 + i]; w[i] = s_vec[9 + i]; wd[i] = s_vec[12 + i]; }
-        double t = *s_time;
-        const R dt = (R)sim_dt;
-        PlanCursor<R> cur;
-        cursor_reset(cur);
-        for (int step = 0; step < n; ++step) {
-          R tp[3], tv[3], ta[3];
-          if (!(sim_dt > 0.0)) cur.idx = 0;
-          sample_plan<R>(t, N, stamps, planP, planV, planA, tp, tv, ta, cur);
-          R th, tq[3];
-          int fl;
-          control_step<R>(ctl, s, t, p, v, a, w, tp, tv, ta, (R)0, (R)0, th, tq, fl);
-          simulator_step<R>(sim, p, v, a, w, t, th, tq, dt, sim_dt, wd);
+      if (tid == 0 && n > 0)
+        fly_steps<R>(ctl, sim, d, N, n, sim_dt, [&](int step, const R* p) {
           if (want_clear) { park[3 * step] = p[0]; park[3 * step + 1] = p[1]; park[3 * step + 2] = p[2]; }
-        }
-        for (int i = 0; i < 3; ++i) { s_vec[i] = p[i]; s_vec[3 + i] = v[i]; s_vec[6 + i] = a[i]; s_vec[9 + i] = w[i]; }
-        *s_time = t;
-        store_ctrl<R>(s_ctrl, s);
-      }
+        });
       __syncthreads();
       if (want_clear && n > 0) {
         R ml = (R)__builtin_huge_val();
@@ -162,36 +127,29 @@ mppi_closed_loop_kernel(DevParams<R> q, CtrlDev<R> ctl, SimDev<R> sim, double pl
           ml = fmin(ml, sqrt(dx * dx + dy * dy + dz * dz) - rad[j]);
         }
         const double wm = wave_min((double)ml);
-        if (lane == 0) red[wave] = wm;
+        if (lane == 0) l.red[wave] = wm;
         __syncthreads();
-        double mc = red[0];
-        for (int w = 1; w < W; ++w) mc = fmin(mc, red[w]);
+        double mc = l.red[0];
+        for (int w = 1; w < W; ++w) mc = fmin(mc, l.red[w]);
         if (tid == 0) s_vec[18] = fmin(s_vec[18], (R)mc);
         __syncthreads();
       }
       s0 += kPark;
     } while (s0 < substeps);
     if (last && plan_last != nullptr)
-      for (int r = tid; r < 3 * rows; r += NT) plan_last[(size_t)b * 3 * rows + r] = planP[r];
+      for (int r = tid; r < 3 * rows; r += NT) plan_last[(size_t)b * 3 * rows + r] = d.planP[r];
     // ---- warm start of the next cycle
-    shift_nominal(q, U, reinterpret_cast<R*>(acc), shift);
+    shift_nominal(q, U, reinterpret_cast<R*>(l.acc), shift);
   }
 
   for (int r = tid; r < rows; r += NT) Ug[(size_t)b * rows + r] = U[r];
   if (tid == 0) {
-    for (int i = 0; i < 3; ++i) { posg[3 * b + i] = s_vec[i]; velg[3 * b + i] = s_vec[3 + i]; attg[3 * b + i] = s_vec[6 + i]; omegag[3 * b + i] = s_vec[9 + i]; }
-    timeg[b] = *s_time;
-    for (int i = 0; i < SE3MPC_CONTROLLER_STATE_WORDS; ++i) stateg[(size_t)b * SE3MPC_CONTROLLER_STATE_WORDS + i] = s_ctrl[i];
+    drone_store<R>(d, b, posg, velg, attg, omegag, timeg, stateg);
     if (want_clear) clearance[b] = s_vec[18];
   }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-static int fail(int rc, const char* what) {
-  set_last_message(what);
-  return rc;
-}
-
 template <typename R>
 static int mppi_closed_loop_impl(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B, int cycles,
                                  int substeps, double sim_dt, uint32_t cycle_base, int shift, int S, int iters, double sigma, double temperature,
@@ -205,15 +163,11 @@ static int mppi_closed_loop_impl(const se3mpc_params* p, const se3mpc_controller
   if (rc) return fail(rc, "se3mpc_mppi_closed_loop: invalid se3mpc_controller_params");
   rc = check_simulator_params(sp);
   if (rc) return fail(rc, "se3mpc_mppi_closed_loop: invalid se3mpc_simulator_params");
-  if (B < 0 || cycles < 0 || substeps < 0 || iters < 0) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_closed_loop: B, cycles, substeps or iters < 0");
+  if (cycles < 0 || substeps < 0) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_closed_loop: cycles or substeps < 0");
   if (shift < 0 || shift > p->horizon) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_closed_loop: shift outside [0, horizon]");
-  if (S < kMinS || S > kMaxS || S % kWave != 0) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_closed_loop: S must be a multiple of 64 in [64, 65536]");
-  if (K < 0 || K > SE3MPC_MAX_SPHERES) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_closed_loop: K outside [0, SE3MPC_MAX_SPHERES]");
   if (wind != nullptr && !(wind_stride == 0 || wind_stride >= 3)) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_closed_loop: wind_stride must be 0 or >= 3");
-  if (!(sigma >= 0.0) || !std::isfinite(sigma)) return fail(SE3MPC_ERR_PARAM, "se3mpc_mppi_closed_loop: sigma must be finite and >= 0");
-  if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(SE3MPC_ERR_PARAM, "se3mpc_mppi_closed_loop: temperature must be finite and > 0");
-  if (!(obstacle_weight >= 0.0) || !std::isfinite(obstacle_weight))
-    return fail(SE3MPC_ERR_PARAM, "se3mpc_mppi_closed_loop: obstacle_weight must be finite and >= 0");
+  rc = check_mppi_args("se3mpc_mppi_closed_loop", p, B, B, S, iters, sigma, temperature, K, obstacle_weight);
+  if (rc) return rc;
   if (!std::isfinite(sim_dt)) return fail(SE3MPC_ERR_PARAM, "se3mpc_mppi_closed_loop: sim_dt must be finite");
   if (B == 0 || cycles == 0) return SE3MPC_OK;
   if (!time || !pos || !vel || !att || !omega || !state || !U || !cost || (p->has_goal && !goal) || (K > 0 && !spheres))

@@ -1,13 +1,15 @@
-// mppi_device.hpp -- device code shared by the MPPI kernels: mppi.hip (one workgroup per problem, every iteration in one launch) and
-// mppi_split.hip (one problem's samples over several workgroups, one launch per iteration).  The noise, the
-// sample, the forward sweep and the weighted pass over a sample range are the same expressions in both files, so the two agree bit for
-// bit wherever their summation orders agree.
+// mppi_device.hpp -- code shared by the MPPI kernels: mppi.hip (one workgroup per problem, every iteration in one launch),
+// mppi_split.hip (one problem's samples over several workgroups, one launch per iteration) and mppi_closed_loop.hip (the planner inside
+// the closed loop).  The noise, the sample, the forward sweep, the weighted pass over a sample range and the
+// update of the nominal are defined once, here, so the files agree bit for bit wherever their summation orders agree; so are the
+// argument rules their entry points have in common (check_mppi_args).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 
 #include "se3mpc_common.hpp"
 #include "closed_loop_device.hpp"
@@ -173,6 +175,23 @@ __host__ __device__ inline Lds lds_layout(int N, int K, int W, size_t esz) {
   return l;
 }
 
+// The image as pointers
+template <typename R>
+struct LdsView {
+  double *acc, *part, *red;
+  R *U, *sph;
+};
+template <typename R>
+__device__ __forceinline__ LdsView<R> lds_view(unsigned char* lds_raw, const Lds& L) {
+  LdsView<R> v;
+  v.acc = reinterpret_cast<double*>(lds_raw + L.acc);
+  v.part = reinterpret_cast<double*>(lds_raw + L.part);
+  v.red = reinterpret_cast<double*>(lds_raw + L.red);
+  v.U = reinterpret_cast<R*>(lds_raw + L.U);
+  v.sph = reinterpret_cast<R*>(lds_raw + L.sph);
+  return v;
+}
+
 // The sphere table into LDS as (cx, cy, cz, (r + margin)^2); the caller's __syncthreads() publishes it
 template <typename R>
 __device__ __forceinline__ void stage_spheres(const DevParams<R>& q, const R* __restrict__ spheres, int K, R* sph) {
@@ -249,6 +268,19 @@ __device__ __forceinline__ double weighted_pass(const Ctx<R>& c, const R* U, int
   return m;
 }
 
+// The update after a weighted pass over ALL samples of an iteration: U <- the weighted mean acc / acc[3N] (the clip only guards the
+// rounding of the division: a mean of in-box samples is in the box; no finite cost: U stays), the pass's minimum m to trace[at]
+// (trace null: none).  Ends with the workgroup synchronised on U.
+template <typename R>
+__device__ __forceinline__ void nominal_update(const DevParams<R>& q, const double* acc, R* U, double m, R* trace, size_t at) {
+  const int rows = 3 * q.N, NT = (int)blockDim.x, tid = (int)threadIdx.x;
+  const double wsum = acc[rows];
+  for (int r = tid; r < rows; r += NT)
+    if (wsum > 0.0) U[r] = box_clip(q, r % 3, (R)(acc[r] / wsum));
+  if (tid == 0 && trace != nullptr) trace[at] = (R)m;
+  __syncthreads();
+}
+
 // The receding-horizon warm start of the nominal in LDS, by the whole workgroup: U[k] <- U[k + shift] for k < N - shift, (0, 0, hover) for
 // the rows behind (shift = 0 keeps U, shift = N resets it).  tmp: LDS scratch of 3N values; U is visible to every lane on return.
 template <typename R>
@@ -271,6 +303,41 @@ __device__ __forceinline__ void write_nominal_cost(const Ctx<R>& c, int p, uint3
     cost_out[p] = cf;
     if (keys != nullptr) keys[p] = ((uint64_t)orderable_bits((float)cf) << 32) | (uint64_t)(index_base + (uint32_t)p);
   }
+}
+
+// ---- host side: the argument rules the MPPI entry points share -------------------------------------------------------------------------
+// fn: the entry point's name, put in front of the message
+static int fail(int rc, const char* what, const char* fn = nullptr) {
+  char msg[160];
+  if (fn != nullptr) {
+    std::snprintf(msg, sizeof(msg), "%s: %s", fn, what);
+    what = msg;
+  }
+  set_last_message(what);
+  return rc;
+}
+
+// The batch and the sample set (every entry point)
+static int check_mppi_batch(const char* fn, const se3mpc_params* p, int nprob, int ld, int S, double sigma) {
+  if (p == nullptr) return fail(SE3MPC_ERR_NULL, "params is NULL", fn);
+  const int rc = check_params_impl(p);
+  if (rc != SE3MPC_OK) return fail(rc, "invalid params", fn);
+  if (nprob < 0 || ld < nprob) return fail(SE3MPC_ERR_SHAPE, "batch size < 0 or leading dimension < batch size", fn);
+  if (S < kMinS || S > kMaxS || S % kWave != 0) return fail(SE3MPC_ERR_SHAPE, "S outside [64, 65536] or not a multiple of 64", fn);
+  if (!(sigma >= 0.0) || !std::isfinite(sigma)) return fail(SE3MPC_ERR_PARAM, "sigma must be finite and >= 0", fn);
+  return SE3MPC_OK;
+}
+
+// ... and the planner's own (se3mpc_mppi_*, se3mpc_mppi_split_*, se3mpc_mppi_closed_loop_*), in the order se3mpc_mppi_* checks them
+static int check_mppi_args(const char* fn, const se3mpc_params* p, int nprob, int ld, int S, int iters, double sigma, double temperature, int K,
+                           double obstacle_weight) {
+  const int rc = check_mppi_batch(fn, p, nprob, ld, S, sigma);
+  if (rc) return rc;
+  if (iters < 0) return fail(SE3MPC_ERR_SHAPE, "iters < 0", fn);
+  if (K < 0 || K > SE3MPC_MAX_SPHERES) return fail(SE3MPC_ERR_SHAPE, "K outside [0, SE3MPC_MAX_SPHERES]", fn);
+  if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(SE3MPC_ERR_PARAM, "temperature must be finite and > 0", fn);
+  if (!(obstacle_weight >= 0.0) || !std::isfinite(obstacle_weight)) return fail(SE3MPC_ERR_PARAM, "obstacle_weight must be finite and >= 0", fn);
+  return SE3MPC_OK;
 }
 
 }  // namespace mppi

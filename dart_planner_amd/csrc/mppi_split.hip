@@ -82,16 +82,13 @@ mppi_split_iter_kernel(DevParams<R> q, int ld, int Sg, int it, R sigma, double i
   const int tid = (int)threadIdx.x;
   const int j = (int)blockIdx.x, G = (int)gridDim.x, p = (int)blockIdx.y, nprob = (int)gridDim.y;
   const Lds L = lds_layout(N, K, W, sizeof(R));
-  double* acc = reinterpret_cast<double*>(lds_raw + L.acc);
-  double* part = reinterpret_cast<double*>(lds_raw + L.part);
-  double* red = reinterpret_cast<double*>(lds_raw + L.red);
-  R* U = reinterpret_cast<R*>(lds_raw + L.U);
-  R* sph = reinterpret_cast<R*>(lds_raw + L.sph);
+  const LdsView<R> l = lds_view<R>(lds_raw, L);
+  R* U = l.U;
   double* fs = reinterpret_cast<double*>(lds_raw + L.total);
   const size_t prob = split_problem_doubles(N, G);
   double* mine = workspace + ((size_t)(it & 1) * nprob + p) * prob;                 // this launch writes here
   const double* theirs = workspace + ((size_t)((it & 1) ^ 1) * nprob + p) * prob;   // the previous launch wrote here
-  stage_spheres(q, spheres, K, sph);
+  stage_spheres(q, spheres, K, l.sph);
   if (it == 0) {
     for (int r = tid; r < rows; r += NT) U[r] = U_in[(size_t)r * ld + p];
     __syncthreads();
@@ -99,11 +96,11 @@ mppi_split_iter_kernel(DevParams<R> q, int ld, int Sg, int it, R sigma, double i
     const double m = fold_partials<R>(q, theirs, G, inv_lam, fs, U);
     if (j == 0 && tid == 0 && trace != nullptr) trace[(size_t)(it - 1) * ld + p] = (R)m;
   }
-  Ctx<R> c = load_ctx(q, ld, p, key0, key1, index_base + (uint32_t)p, p0, v0, goal, U, sph, K, w_obs);
+  Ctx<R> c = load_ctx(q, ld, p, key0, key1, index_base + (uint32_t)p, p0, v0, goal, U, l.sph, K, w_obs);
   c.g = iter_base + (iter_offset != nullptr ? *iter_offset : 0u) + (uint32_t)it;
-  const double m = weighted_pass<R>(c, U, j * Sg, Sg, sigma, inv_lam, acc, part, red);
+  const double m = weighted_pass<R>(c, U, j * Sg, Sg, sigma, inv_lam, l.acc, l.part, l.red);
   double* slot = mine + (size_t)j * split_partial_doubles(N);
-  for (int r = tid; r <= rows; r += NT) slot[r] = acc[r];
+  for (int r = tid; r <= rows; r += NT) slot[r] = l.acc[r];
   if (tid == 0) slot[rows + 1] = m;
   if (j == 0)
     for (int r = tid; r < rows; r += NT) mine[(size_t)G * split_partial_doubles(N) + r] = (double)U[r];
@@ -121,10 +118,10 @@ mppi_split_finish_kernel(DevParams<R> q, int ld, int G, int iters, double inv_la
   const int tid = (int)threadIdx.x, wave = tid / kWave;
   const int p = (int)blockIdx.x, nprob = (int)gridDim.x;
   const Lds L = lds_layout(N, K, NT / kWave, sizeof(R));
-  R* U = reinterpret_cast<R*>(lds_raw + L.U);
-  R* sph = reinterpret_cast<R*>(lds_raw + L.sph);
+  const LdsView<R> l = lds_view<R>(lds_raw, L);
+  R* U = l.U;
   double* fs = reinterpret_cast<double*>(lds_raw + L.total);
-  stage_spheres(q, spheres, K, sph);
+  stage_spheres(q, spheres, K, l.sph);
   if (iters == 0) {
     for (int r = tid; r < rows; r += NT) U[r] = U_in[(size_t)r * ld + p];
     __syncthreads();
@@ -133,17 +130,12 @@ mppi_split_finish_kernel(DevParams<R> q, int ld, int G, int iters, double inv_la
     const double m = fold_partials<R>(q, theirs, G, inv_lam, fs, U);
     if (tid == 0 && trace != nullptr) trace[(size_t)(iters - 1) * ld + p] = (R)m;
   }
-  Ctx<R> c = load_ctx(q, ld, p, 0u, 0u, index_base + (uint32_t)p, p0, v0, goal, U, sph, K, w_obs);
+  Ctx<R> c = load_ctx(q, ld, p, 0u, 0u, index_base + (uint32_t)p, p0, v0, goal, U, l.sph, K, w_obs);
   if (wave == 0) write_nominal_cost(c, p, index_base, cost_out, keys);
   for (int r = tid; r < rows; r += NT) U_out[(size_t)r * ld + p] = U[r];
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-static int fail(int rc, const char* what) {
-  set_last_message(what);
-  return rc;
-}
-
 static size_t workspace_bytes(int horizon, int nprob, int splits) {
   if (horizon < 1 || horizon > SE3MPC_MAX_HORIZON || nprob < 0 || splits < 1) return 0;
   return (size_t)2 * (size_t)nprob * split_problem_doubles(horizon, splits) * sizeof(double);
@@ -154,18 +146,8 @@ static int mppi_split_impl(const se3mpc_params* p, int nprob, int ld, int S, int
                            uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const R* p0, const R* v0, const R* goal,
                            const R* U_in, R* U_out, const R* spheres, int K, double obstacle_weight, R* cost, R* trace, uint64_t* keys,
                            int splits, void* workspace, size_t workspace_size, void* stream) {
-  // the rules of se3mpc_mppi_* (mppi.hip), in its order
-  if (p == nullptr) return fail(SE3MPC_ERR_NULL, "se3mpc_mppi_split: params is NULL");
-  const int rc = check_params_impl(p);
-  if (rc != SE3MPC_OK) return fail(rc, "se3mpc_mppi_split: invalid params");
-  if (nprob < 0 || ld < nprob) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_split: nprob < 0 or ld < nprob");
-  if (S < kMinS || S > kMaxS || S % kWave != 0) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_split: S outside [64, 65536] or not a multiple of 64");
-  if (!(sigma >= 0.0) || !std::isfinite(sigma)) return fail(SE3MPC_ERR_PARAM, "se3mpc_mppi_split: sigma must be finite and >= 0");
-  if (iters < 0) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_split: iters < 0");
-  if (K < 0 || K > SE3MPC_MAX_SPHERES) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_split: K outside [0, SE3MPC_MAX_SPHERES]");
-  if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(SE3MPC_ERR_PARAM, "se3mpc_mppi_split: temperature must be finite and > 0");
-  if (!(obstacle_weight >= 0.0) || !std::isfinite(obstacle_weight))
-    return fail(SE3MPC_ERR_PARAM, "se3mpc_mppi_split: obstacle_weight must be finite and >= 0");
+  const int rc = check_mppi_args("se3mpc_mppi_split", p, nprob, ld, S, iters, sigma, temperature, K, obstacle_weight);
+  if (rc) return rc;
   // the split's own
   if (splits < 1) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_split: splits < 1");
   if (S % (kWave * (long long)splits) != 0) return fail(SE3MPC_ERR_SHAPE, "se3mpc_mppi_split: S is not a multiple of 64 * splits");

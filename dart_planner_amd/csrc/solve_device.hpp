@@ -28,6 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <time.h>
 
+#include <type_traits>
+
 #include "se3mpc_common.hpp"
 #include <se3mpc_wave_ops.hpp>
 
@@ -478,6 +480,19 @@ __host__ __device__ constexpr int small_doubles(int m) { return (7 * m * m + 10 
 template <typename IO> __host__ __device__ constexpr int pair_row_values() { return sizeof(IO) == 4 ? 20 : 18; }
 __host__ __device__ constexpr size_t pairs_offset_bytes(int P, int m) { return ((size_t)P * small_doubles(m) * sizeof(double) + 15) / 16 * 16; }
 
+
+// Lanes per problem at horizon N: the smallest group that holds the horizon (solve_kernel.hip says why, and may widen it)
+inline int solve_group_for_horizon(int N) { return N <= 8 ? 8 : (N <= 16 ? 16 : (N <= 32 ? 32 : 64)); }
+
+// Calls launch(std::integral_constant<int, G>{}) for a group size G of {8, 16, 32, 64} (anything else: 64): the one place a runtime group
+// size becomes the kernels' template parameter.  `launch` is instantiated for exactly these four.
+template <typename F>
+void dispatch_group(int G, F&& launch) {
+  if (G == 8) return launch(std::integral_constant<int, 8>{});
+  if (G == 16) return launch(std::integral_constant<int, 16>{});
+  if (G == 32) return launch(std::integral_constant<int, 32>{});
+  launch(std::integral_constant<int, 64>{});
+}
 
 // bytes of LDS one wavefront's solver image needs with storage for m L-BFGS pairs at G lanes per problem
 static inline size_t solve_lds_bytes(int m, int G, size_t io_size) {

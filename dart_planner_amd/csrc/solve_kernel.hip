@@ -131,7 +131,6 @@ solve_kernel(SolveDev q, int B, const IO* __restrict__ p0g, const IO* __restrict
 
 static int g_solver_variant = 0;   // bit 0: published sequential Cauchy search also while the memory is empty; bits 8-15: forced group size (0 = automatic)
 
-
 // Group size for problems of horizon N: the smallest group that holds the horizon packs the most problems into a wavefront -- the
 // group-uniform algebra (line search, middle matrices, reductions) is then shared by 64 / G problems.  Measured on MI355X
 // (profiles/r03_solve_group_probe.txt): the smallest group wins at every batch size from 1 K problems up, also where a wider group
@@ -140,7 +139,7 @@ static int g_solver_variant = 0;   // bit 0: published sequential Cauchy search 
 // its neighbours' third) is about an eighth of a wavefront's time.
 static int solve_group_size(int N) {
   const int forced = (g_solver_variant >> 8) & 0xFF;
-  const int G = N <= 8 ? 8 : (N <= 16 ? 16 : (N <= 32 ? 32 : 64));
+  const int G = solve_group_for_horizon(N);
   if (forced == 8 || forced == 16 || forced == 32 || forced == 64) return forced >= G ? forced : G;
   return G;
 }
@@ -165,23 +164,18 @@ int solve_impl(const se3mpc_params* p, int B, const IO* p0, const IO* v0, const 
   const int G = (B == 1 && ((g_solver_variant >> 8) & 0xFF) == 0) ? kWave : solve_group_size(q.N);
   const int waves = (int)(((long)B * G + kWave - 1) / kWave);
   if (done != nullptr && waves != 1) return SE3MPC_ERR_SHAPE;
-#define SE3MPC_SOLVE_CASE(GG)                                                                                               \
-  {                                                                                                                         \
-    /* the attribute is raised once per instantiation and size, not on every plan (it is a driver call) */                  \
-    static size_t lds_allowed = 64 * 1024;                                                                                  \
-    if (solve_lds_bytes(q.mlds, GG, sizeof(IO)) > lds_allowed) {                                                            \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<IO, GG>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)solve_lds_bytes(q.mlds, GG, sizeof(IO)));                                               \
-      lds_allowed = solve_lds_bytes(q.mlds, GG, sizeof(IO));                                                                \
-    }                                                                                                                       \
-  }                                                                                                                         \
-  hipLaunchKernelGGL((solve_kernel<IO, GG>), dim3(waves), dim3(kWave), solve_lds_bytes(q.mlds, GG, sizeof(IO)), s, q, B, p0, \
-                     v0, goal, x0, X, info, acc, att, rates, thrust, done, ticket)
-#define SE3MPC_SOLVE_LAUNCH()               \
-  if (G == 8) { SE3MPC_SOLVE_CASE(8); }         \
-  else if (G == 16) { SE3MPC_SOLVE_CASE(16); }  \
-  else if (G == 32) { SE3MPC_SOLVE_CASE(32); }  \
-  else { SE3MPC_SOLVE_CASE(64); }
+  auto launch = [&](auto g) {
+    constexpr int GG = decltype(g)::value;
+    const size_t lds = solve_lds_bytes(q.mlds, GG, sizeof(IO));
+    // the attribute is raised once per instantiation and size, not on every plan (it is a driver call)
+    static size_t lds_allowed = 64 * 1024;
+    if (lds > lds_allowed) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<IO, GG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      lds_allowed = lds;
+    }
+    hipLaunchKernelGGL((solve_kernel<IO, GG>), dim3(waves), dim3(kWave), lds, s, q, B, p0, v0, goal, x0, X, info, acc, att, rates, thrust, done,
+                       ticket);
+  };
   // Two tiers buy occupancy (two resident wavefronts per SIMD): the first gets the most pairs (<= 4, >= 2) whose LDS still lets
   // eight wavefronts share a CU's 160 KiB.  While every wavefront of the launch is resident at once even with the full memory's LDS
   // footprint (256 CUs x the wavefronts whose LDS fits a CU, at most one per SIMD) there is nothing to buy, and a single launch
@@ -193,14 +187,12 @@ int solve_impl(const se3mpc_params* p, int B, const IO* p0, const IO* v0, const 
   if (full_per_cu > 4) full_per_cu = 4;
   const bool two_tier = info != nullptr && q.m > fast && (size_t)waves > 256 * full_per_cu;    // the tiers talk through info[].task
   q.mlds = two_tier ? fast : q.m;
-  SE3MPC_SOLVE_LAUNCH();
+  dispatch_group(G, launch);
   rc = launch_status("se3mpc_solve");
   if (rc != SE3MPC_OK || !two_tier) return rc;
   q.mlds = q.m;
   q.only_overflow = 1;
-  SE3MPC_SOLVE_LAUNCH();
-#undef SE3MPC_SOLVE_LAUNCH
-#undef SE3MPC_SOLVE_CASE
+  dispatch_group(G, launch);
   return launch_status("se3mpc_solve(second tier)");
 }
 

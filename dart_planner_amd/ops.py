@@ -99,6 +99,13 @@ class Ops:
                 raise ValueError("all lane-layout operands must share dtype and leading dimension")
         return suf
 
+    def _spheres(self, spheres, suf) -> int:
+        """A sphere table (K <= SE3MPC_MAX_SPHERES, 4) rows (cx, cy, cz, r) of the call's dtype -> K."""
+        self.be.check(spheres, "spheres")
+        if spheres.ndim != 2 or spheres.shape[1] != 4 or spheres.shape[0] > SE3MPC_MAX_SPHERES or self.be.suffix(spheres) != suf:
+            raise ValueError(f"spheres: expected (K<={SE3MPC_MAX_SPHERES}, 4) {suf}, got {tuple(spheres.shape)}")
+        return spheres.shape[0]
+
     @staticmethod
     def _B(ld: int, B: Optional[int]) -> int:
         B = ld if B is None else int(B)
@@ -284,9 +291,7 @@ class Ops:
         if params.has_goal:
             self._lane(goal, 3, "goal")
         suf = self._same(T, p0, v0, goal if params.has_goal else None)
-        self.be.check(spheres, "spheres")
-        if spheres.ndim != 2 or spheres.shape[1] != 4 or spheres.shape[0] > SE3MPC_MAX_SPHERES or self.be.suffix(spheres) != suf:
-            raise ValueError(f"spheres: expected (K<={SE3MPC_MAX_SPHERES}, 4) {suf}, got {tuple(spheres.shape)}")
+        self._spheres(spheres, suf)
         ld = T.shape[1]
         if out is not None:
             cost, gradT, cmin, viol = out
@@ -316,9 +321,7 @@ class Ops:
         if params.has_goal:
             self.be.check(goal, "goal")
         suf = self.be.suffix(T)
-        self.be.check(spheres, "spheres")
-        if spheres.ndim != 2 or spheres.shape[1] != 4 or spheres.shape[0] > SE3MPC_MAX_SPHERES or self.be.suffix(spheres) != suf:
-            raise ValueError(f"spheres: expected (K<={SE3MPC_MAX_SPHERES}, 4) {suf}, got {tuple(spheres.shape)}")
+        self._spheres(spheres, suf)
         self.lib.call("rollout_obstacles_batched", suf, ld, ld, nb, self.be.ptr(p0), self.be.ptr(v0),
                       self.be.ptr(goal if params.has_goal else None), self.be.ptr(T), self.be.ptr(cost), self.be.ptr(gradT),
                       self.be.ptr(spheres), spheres.shape[0], self.be.ptr(cmin), self.be.ptr(viol), self.be.ptr(wave_keys),
@@ -353,9 +356,7 @@ class Ops:
         cost_first = self.be.empty(lead + (ld,), suf) if want_first_cost else None
         nB = self._B(ld, B)
         if spheres is not None:
-            self.be.check(spheres, "spheres")
-            if spheres.ndim != 2 or spheres.shape[1] != 4 or spheres.shape[0] > SE3MPC_MAX_SPHERES or self.be.suffix(spheres) != suf:
-                raise ValueError(f"spheres: expected (K<={SE3MPC_MAX_SPHERES}, 4) {suf}, got {tuple(spheres.shape)}")
+            self._spheres(spheres, suf)
             penalty = self.be.empty(lead + (ld,), suf) if want_penalty else None
             self.lib.call("rollout_iterate_obstacles", suf, nB, ld, nb, int(iters), float(step), self.be.ptr(p0), self.be.ptr(v0),
                           self.be.ptr(goal if params.has_goal else None), self.be.ptr(T), self.be.ptr(T_out), self.be.ptr(cost_first),
@@ -440,10 +441,7 @@ class Ops:
         N = params.horizon
         K = 0
         if spheres is not None:
-            self.be.check(spheres, "spheres")
-            if spheres.ndim != 2 or spheres.shape[1] != 4 or spheres.shape[0] > SE3MPC_MAX_SPHERES or self.be.suffix(spheres) != suf:
-                raise ValueError(f"spheres: expected (K<={SE3MPC_MAX_SPHERES}, 4) {suf}, got {tuple(spheres.shape)}")
-            K = spheres.shape[0]
+            K = self._spheres(spheres, suf)
         if out is not None:
             U_out, cost, trace, keys = out
         else:
@@ -545,6 +543,21 @@ class Ops:
         self.lib.controller_reset(cp, B, self.be.ptr(st), self.be.stream())
         return st
 
+    def _ctrl_state(self, state, B):
+        """The controller records of B drones: float64 (B, 12)."""
+        self.be.check(state, "state")
+        if tuple(state.shape) != (B, CONTROLLER_STATE_WORDS) or self.be.suffix(state) != "f64":
+            raise ValueError("state: float64 (B, 12)")
+
+    def _wind(self, wind, B, suf) -> int:
+        """A wind operand of the fused loops: None, one (3,) vector for all drones or (B, 3) rows, of the call's dtype -> its row stride."""
+        if wind is None:
+            return 0
+        self.be.check(wind, "wind")
+        if self.be.suffix(wind) != suf or wind.shape[-1] != 3 or (wind.ndim == 2 and wind.shape[0] != B):
+            raise ValueError("wind: (3,) or (B, 3)")
+        return 3 if wind.ndim == 2 else 0
+
     def _rows3(self, a, B, name, suf=None):
         self.be.check(a, name)
         if tuple(a.shape) != (B, 3) or (suf is not None and self.be.suffix(a) != suf):
@@ -594,9 +607,7 @@ class Ops:
                 self.be.check(a, nm)
                 if tuple(a.shape) != (B,) or self.be.suffix(a) != suf:
                     raise ValueError(f"{nm}: expected ({B},) {suf}")
-        self.be.check(state, "state")
-        if tuple(state.shape) != (B, CONTROLLER_STATE_WORDS) or self.be.suffix(state) != "f64":
-            raise ValueError("state: float64 (B, 12)")
+        self._ctrl_state(state, B)
         thrust, torque = self.be.empty((B,), suf), self.be.empty((B, 3), suf)
         flags = self.be.empty((B,), "i32")
         self.lib.loop_call("control_fast", suf, cp, float(vehicle_mass), float(vehicle_gravity), B, float(dt), self.be.ptr(pos), self.be.ptr(vel),
@@ -618,12 +629,7 @@ class Ops:
         self.be.check(state, "state"); self.be.check(time, "time")
         if tuple(state.shape) != (B, CONTROLLER_STATE_WORDS) or self.be.suffix(state) != "f64" or tuple(time.shape) != (B,) or self.be.suffix(time) != "f64":
             raise ValueError("state: float64 (B, 12); time: float64 (B,)")
-        w_stride = 0
-        if wind is not None:
-            self.be.check(wind, "wind")
-            if self.be.suffix(wind) != suf or wind.shape[-1] != 3 or (wind.ndim == 2 and wind.shape[0] != B):
-                raise ValueError("wind: (3,) or (B, 3)")
-            w_stride = 3 if wind.ndim == 2 else 0
+        w_stride = self._wind(wind, B, suf)
         N = params.horizon
         over = self.be.empty((1,), "i32")
         X = self.be.empty((B, 9 * N), suf) if want_last_plan else None
@@ -656,18 +662,10 @@ class Ops:
             raise ValueError("state: float64 (B, 12); time: float64 (B,)")
         if tuple(U.shape) != (B, N, 3) or self.be.suffix(U) != suf:
             raise ValueError(f"U: expected ({B}, {N}, 3) {suf}, got {tuple(U.shape)}")
-        w_stride = 0
-        if wind is not None:
-            self.be.check(wind, "wind")
-            if self.be.suffix(wind) != suf or wind.shape[-1] != 3 or (wind.ndim == 2 and wind.shape[0] != B):
-                raise ValueError("wind: (3,) or (B, 3)")
-            w_stride = 3 if wind.ndim == 2 else 0
+        w_stride = self._wind(wind, B, suf)
         K = 0
         if spheres is not None:
-            self.be.check(spheres, "spheres")
-            if spheres.ndim != 2 or spheres.shape[1] != 4 or spheres.shape[0] > SE3MPC_MAX_SPHERES or self.be.suffix(spheres) != suf:
-                raise ValueError(f"spheres: expected (K<={SE3MPC_MAX_SPHERES}, 4) {suf}, got {tuple(spheres.shape)}")
-            K = spheres.shape[0]
+            K = self._spheres(spheres, suf)
         if clearance is not None:
             self.be.check(clearance, "clearance")
             if tuple(clearance.shape) != (B,) or self.be.suffix(clearance) != suf:
@@ -694,9 +692,7 @@ class Ops:
         B = vel_error.shape[0]
         suf = self.be.suffix(vel_error)
         self._rows3(vel_error, B, "vel_error", suf)
-        self.be.check(state, "state")
-        if tuple(state.shape) != (B, CONTROLLER_STATE_WORDS) or self.be.suffix(state) != "f64":
-            raise ValueError("state: float64 (B, 12)")
+        self._ctrl_state(state, B)
         if saturation is not None:
             self.be.check(saturation, "saturation")
             if tuple(saturation.shape) != (B,) or not str(saturation.dtype).endswith("int32"):     # (a float32 (B,) array would be read as flag bits)
@@ -712,9 +708,7 @@ class Ops:
         suf = self.be.suffix(att)
         for a, nm in ((att, "att"), (omega, "omega"), (b3_des, "b3_des")):
             self._rows3(a, B, nm, suf)
-        self.be.check(state, "state")
-        if tuple(state.shape) != (B, CONTROLLER_STATE_WORDS) or self.be.suffix(state) != "f64":
-            raise ValueError("state: float64 (B, 12)")
+        self._ctrl_state(state, B)
         mat = None
         if inertia is not None:
             m = np.asarray(inertia, dtype=np.float64)

@@ -30,7 +30,7 @@ def scene(B, dtype, seed=5):
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
-@pytest.mark.parametrize("N,B", [(6, 19), (13, 5), (30, 3)])
+@pytest.mark.parametrize("N,B", [(6, 19), (13, 5), (30, 3), (33, 2)])
 def test_fused_monte_carlo_equals_the_two_launch_form(cpu_ops, dtype, N, B):
     from dart_planner_amd.capi import Params
     from dart_planner_amd.control.closed_loop import ClosedLoopMonteCarlo

@@ -408,13 +408,14 @@ def test_device_plan_travels_in_the_reference_envelope(gpu_ops):
 def test_monte_carlo_in_one_launch_equals_the_two_launch_form(gpu_ops, prec):
     """se3mpc_monte_carlo_*: every planning cycle of every drone inside ONE kernel (each drone pays only for its own slow solves) ==
     alternating se3mpc_solve_* and se3mpc_closed_loop_* (ClosedLoopMonteCarlo.run), BIT FOR BIT -- it is the same code: BASELINE config 5's
-    named shape (4096 runs x 33 cycles x 15 steps), a ragged batch at another horizon, shared / no wind."""
+    named shape (4096 runs x 33 cycles x 15 steps), ragged batches at other horizons (33: the smallest with 64 lanes per drone), shared /
+    no wind."""
     import torch
     from dart_planner_amd.capi import Params
     from dart_planner_amd.control.closed_loop import ClosedLoopMonteCarlo
     dtype = torch.float32 if prec == "f32" else torch.float64
     dev = gpu_ops.be.device
-    for N, B, cycles, substeps in ((6, 4096, 33, 15), (13, 77, 6, 7), (30, 131, 5, 4)):
+    for N, B, cycles, substeps in ((6, 4096, 33, 15), (13, 77, 6, 7), (30, 131, 5, 4), (33, 2, 2, 3)):
         mc = ClosedLoopMonteCarlo(gpu_ops, Params.reference_defaults(horizon=N))
         g = torch.Generator(device=dev); g.manual_seed(5)
         p0 = torch.tensor([0.0, 0.0, 2.0], dtype=dtype, device=dev).repeat(B, 1) + 0.2 * torch.randn(B, 3, dtype=dtype, device=dev, generator=g)

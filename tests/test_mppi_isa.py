@@ -1,52 +1,18 @@
 """CPU: dart_planner_amd/csrc/mppi.hip compiled to gfx950 ISA with the Makefile's own HIPFLAGS: every MPPI kernel instantiation keeps
 its registers (no VGPR spills, no scratch, no AGPRs) within the four-wavefronts-per-SIMD budget its __launch_bounds__ asks for.
 The VGPR counts printed here are the ones DESIGN.md 5.8 quotes."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dart_planner_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
-def makefile_hipflags():
-    """HIPFLAGS of csrc/Makefile with its make variables substituted (continuation lines joined)."""
-    txt = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
-    m = re.search(r"^HIPFLAGS\s*:=\s*(.*)$", txt, flags=re.M)
-    assert m, "HIPFLAGS not found in csrc/Makefile"
-    subst = {"ARCH": "gfx950", "ROOT": ROOT, "EXTRA_HIPFLAGS": ""}
-    return re.sub(r"\$\((\w+)\)", lambda v: subst[v.group(1)], m.group(1)).split()
+from isa_checks import compile_isa, kernel_stats
 
 
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "mppi.s")
-    subprocess.run([HIPCC] + makefile_hipflags() + ["--cuda-device-only", "-S", os.path.join(CSRC, "mppi.hip"), "-o", out], check=True,
-                   capture_output=True)
-    return open(out).read()
-
-
-def kernel_stats(asm):
-    """{kernel symbol: {NumVgprs, NumAgprs, ScratchSize, Occupancy}} from the per-function comment blocks, and the metadata spill counts."""
-    stats = {}
-    for m in re.finditer(r"^(_Z\w*mppi\w*):[^\n]*$(.*?)^; Occupancy: (\d+)", asm, flags=re.M | re.S):
-        body = m.group(2)
-        get = lambda key: int(re.findall(rf"; {key}: (\d+)", body)[-1])
-        stats[m.group(1)] = dict(vgpr=get("NumVgprs"), agpr=get("NumAgprs"), scratch=get("ScratchSize"), occupancy=int(m.group(3)))
-    for m in re.finditer(r"\.name:\s+(_Z\w*mppi\w*).*?\.vgpr_spill_count:\s+(\d+)", asm, flags=re.S):
-        if m.group(1) in stats:
-            stats[m.group(1)]["vgpr_spill"] = int(m.group(2))
-    return stats
+    return compile_isa("mppi", tmp_path_factory)
 
 
 def test_mppi_kernels_keep_their_registers(isa):
-    st = kernel_stats(isa)
+    st = kernel_stats(isa, "mppi")
     names = sorted(st)
     assert any("mppi_kernelIf" in n for n in names) and any("mppi_kernelId" in n for n in names), names
     assert any("mppi_samples_kernelIf" in n for n in names) and any("mppi_samples_kernelId" in n for n in names), names

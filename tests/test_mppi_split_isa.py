@@ -4,51 +4,19 @@ four-wavefronts-per-SIMD budget its __launch_bounds__ asks for -- the budget mpp
 The VGPR counts printed here are the ones DESIGN.md 5.8b quotes."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "dart_planner_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
-def makefile_hipflags():
-    """HIPFLAGS of csrc/Makefile with its make variables substituted (continuation lines joined)."""
-    txt = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
-    m = re.search(r"^HIPFLAGS\s*:=\s*(.*)$", txt, flags=re.M)
-    assert m, "HIPFLAGS not found in csrc/Makefile"
-    subst = {"ARCH": "gfx950", "ROOT": ROOT, "EXTRA_HIPFLAGS": ""}
-    return re.sub(r"\$\((\w+)\)", lambda v: subst[v.group(1)], m.group(1)).split()
+from isa_checks import CSRC, compile_isa, kernel_stats
 
 
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
-    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
-        pytest.skip("hipcc not available")
-    src = os.path.join(CSRC, "mppi_split.hip")
-    assert os.path.exists(src), "dart_planner_amd/csrc/mppi_split.hip is missing"
-    out = str(tmp_path_factory.mktemp("isa") / "mppi_split.s")
-    subprocess.run([HIPCC] + makefile_hipflags() + ["--cuda-device-only", "-S", src, "-o", out], check=True, capture_output=True)
-    return open(out).read()
-
-
-def kernel_stats(asm):
-    """{kernel symbol: {vgpr, agpr, scratch, occupancy, vgpr_spill}} from the per-function comment blocks and the metadata."""
-    stats = {}
-    for m in re.finditer(r"^(_Z\w*mppi_split\w*):[^\n]*$(.*?)^; Occupancy: (\d+)", asm, flags=re.M | re.S):
-        body = m.group(2)
-        get = lambda key: int(re.findall(rf"; {key}: (\d+)", body)[-1])
-        stats[m.group(1)] = dict(vgpr=get("NumVgprs"), agpr=get("NumAgprs"), scratch=get("ScratchSize"), occupancy=int(m.group(3)))
-    for m in re.finditer(r"\.name:\s+(_Z\w*mppi_split\w*).*?\.vgpr_spill_count:\s+(\d+)", asm, flags=re.S):
-        if m.group(1) in stats:
-            stats[m.group(1)]["vgpr_spill"] = int(m.group(2))
-    return stats
+    return compile_isa("mppi_split", tmp_path_factory)
 
 
 def test_split_kernels_keep_their_registers(isa):
-    st = kernel_stats(isa)
+    st = kernel_stats(isa, "mppi_split")
     names = sorted(st)
     for kernel in ("mppi_split_iter_kernelIf", "mppi_split_iter_kernelId", "mppi_split_finish_kernelIf", "mppi_split_finish_kernelId"):
         assert sum(kernel in n for n in names) == 1, (kernel, names)
@@ -62,9 +30,11 @@ def test_split_kernels_keep_their_registers(isa):
 
 
 def test_the_device_code_is_shared_not_copied():
-    """mppi.hip and mppi_split.hip take the sampler, the rollout and the weighted pass from csrc/mppi_device.hpp; neither defines them."""
+    """mppi.hip and mppi_split.hip take the sampler, the rollout, the weighted pass, the update, the LDS view and the argument rules from
+    csrc/mppi_device.hpp; neither defines them."""
     header = open(os.path.join(CSRC, "mppi_device.hpp")).read()
-    for name in ("philox4x32_10", "box_muller", "draw", "roll_step", "sample_cost", "box_clip", "orderable_bits", "lds_layout", "weighted_pass"):
+    for name in ("philox4x32_10", "box_muller", "draw", "roll_step", "sample_cost", "box_clip", "orderable_bits", "lds_layout", "weighted_pass", "lds_view",
+                 "nominal_update", "check_mppi_args", "fail"):
         assert re.search(rf"\b{name}\(", header), name
         for f in ("mppi.hip", "mppi_split.hip"):
             src = open(os.path.join(CSRC, f)).read()

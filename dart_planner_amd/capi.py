@@ -140,7 +140,30 @@ class SimulatorParams(C.Structure):
         return p
 
 
+class SmootherParams(C.Structure):
+    """struct se3mpc_smoother_params == the constants of TrajectorySmoother (src/dart_planner/control/trajectory_smoother.py:19-26,
+    :101, :151, :176-179, :329-331)."""
+    _fields_ = [("transition_time", C.c_double), ("velocity_limit", C.c_double), ("acceleration_limit", C.c_double),
+                ("jerk_limit", C.c_double), ("update_dt", C.c_double), ("smoothing_window", C.c_double),
+                ("pos_diff_threshold", C.c_double), ("vel_diff_threshold", C.c_double), ("timeout", C.c_double),
+                ("decay_rate", C.c_double), ("decay_cap", C.c_double)]
+
+    @classmethod
+    def reference_defaults(cls, **overrides) -> "SmootherParams":
+        p = cls(transition_time=0.5, velocity_limit=5.0, acceleration_limit=3.0, jerk_limit=10.0, update_dt=0.01, smoothing_window=0.1,
+                pos_diff_threshold=0.5, vel_diff_threshold=1.0, timeout=2.0, decay_rate=2.0, decay_cap=5.0)
+        for k, v in overrides.items():
+            if k not in dict(cls._fields_):
+                raise AttributeError(f"se3mpc_smoother_params has no field {k!r}")
+            setattr(p, k, float(v))
+        return p
+
+    def copy(self, **overrides) -> "SmootherParams":
+        return type(self).reference_defaults(**{**{k: getattr(self, k) for k, _ in self._fields_}, **overrides})
+
+
 CONTROLLER_STATE_WORDS = 12
+SMOOTHER_STATE_WORDS = 25
 
 _P = C.c_void_p
 _I = C.c_int
@@ -193,7 +216,9 @@ _VOXEL_PLAIN_API = {
 }
 _CP = C.POINTER(ControllerParams)
 _SP = C.POINTER(SimulatorParams)
+_MP = C.POINTER(SmootherParams)
 _LL = C.c_longlong
+_PLAN = [_I, _P, _LL, _P, _LL, _P, _LL, _P, _LL]            # N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA
 # consumer side of the contract: se3mpc_<base>_<suffix>(...)
 _LOOP_TYPED_API = {
     "control": [_CP, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -205,6 +230,10 @@ _LOOP_TYPED_API = {
     "simulator_step": [_SP, _I, _D, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P],
     "closed_loop": [_CP, _SP, _I, _I, _D, _I, _P, _LL, _P, _LL, _P, _LL, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _LL, _I,
                     C.POINTER(C.c_double * 3), _I, _P, _P, _P, _P, _P],
+    "smoother_update": [_MP, _I, _P] + _PLAN + _PLAN + [_P, _P],
+    "smoother_desired": [_MP, _I, _P, _P, _P] + _PLAN + [_P, _P, _P, _P],
+    "closed_loop_smoothed": [_MP, _CP, _SP, _I, _I, _D] + _PLAN + [_P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, C.POINTER(C.c_double * 3),
+                             _P, _P, _P, _P, _P],
     "monte_carlo": [_PP, _CP, _SP, _I, _I, _I, _D, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mppi_closed_loop": [_PP, _CP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _D, _P, _LL,
                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -213,6 +242,8 @@ _PLAIN_API = {
     "se3mpc_controller_default_params": (C.c_int, [_CP]),
     "se3mpc_simulator_default_params": (C.c_int, [_SP]),
     "se3mpc_controller_reset": (C.c_int, [_CP, _I, _P, _P]),
+    "se3mpc_smoother_default_params": (C.c_int, [_MP]),
+    "se3mpc_smoother_reset": (C.c_int, [_I, _P, _P]),
     "se3mpc_abi_version": (C.c_int, []),
     "se3mpc_last_error": (C.c_char_p, []),
     "se3mpc_device_count": (C.c_int, []),
@@ -355,13 +386,21 @@ class Library:
     def controller_reset(self, cp: ControllerParams, B: int, state: int, stream: int) -> None:
         self._check("se3mpc_controller_reset", self._dll.se3mpc_controller_reset(C.byref(cp), B, state, stream))
 
+    def smoother_default_params(self) -> SmootherParams:
+        p = SmootherParams()
+        self._check("se3mpc_smoother_default_params", self._dll.se3mpc_smoother_default_params(C.byref(p)))
+        return p
+
+    def smoother_reset(self, B: int, state: int, stream: int) -> None:
+        self._check("se3mpc_smoother_reset", self._dll.se3mpc_smoother_reset(B, state, stream))
+
     def loop_call(self, base: str, suffix: str, *args) -> None:
         """se3mpc_control_<suffix> / se3mpc_closed_loop_<suffix>; struct arguments are passed by reference here."""
-        a = [C.byref(x) if isinstance(x, (ControllerParams, SimulatorParams, Params)) else x for x in args]
+        a = [C.byref(x) if isinstance(x, (ControllerParams, SimulatorParams, SmootherParams, Params)) else x for x in args]
         self._check(f"se3mpc_{base}_{suffix}", getattr(self._dll, f"se3mpc_{base}_{suffix}")(*a))
 
     def loop_status(self, base: str, suffix: str, *args) -> int:
-        a = [C.byref(x) if isinstance(x, (ControllerParams, SimulatorParams, Params)) else x for x in args]
+        a = [C.byref(x) if isinstance(x, (ControllerParams, SimulatorParams, SmootherParams, Params)) else x for x in args]
         return getattr(self._dll, f"se3mpc_{base}_{suffix}")(*a)
 
     # -- voxel map ----------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 (src/dart_planner/common/di_container_v2.py:488-540, :690-697):
 ``get_container().create_planner_container().get_se3_planner(config=None)`` -> a process-wide
 singleton when no config is given, a fresh instance otherwise; ``create_control_container()
-.get_geometric_controller(tuning_profile)``.  No ZMQ / security / hardware registrations."""
+.get_geometric_controller(tuning_profile)`` / ``.get_trajectory_smoother()`` (:542-545, a singleton).  No ZMQ / security / hardware registrations."""
 import threading
 from typing import Any, Callable, Dict, Optional
 
@@ -48,6 +48,10 @@ class ControlContainer:
     def get_geometric_controller(self, tuning_profile: str = "sitl_optimized"):
         from ..control.geometric_controller import GeometricController
         return GeometricController(tuning_profile=tuning_profile)
+
+    def get_trajectory_smoother(self):
+        from ..control.trajectory_smoother import TrajectorySmoother
+        return self.container.resolve(TrajectorySmoother)
 
 
 _container: Optional[DIContainerV2] = None

@@ -17,8 +17,8 @@ import ctypes as _C
 
 import numpy as np
 
-from .capi import (CONTROLLER_STATE_WORDS, ControllerParams, Library, Params, SimulatorParams, SolveInfo, get_library,
-                   SE3MPC_MAX_SPHERES)
+from .capi import (CONTROLLER_STATE_WORDS, SMOOTHER_STATE_WORDS, ControllerParams, Library, Params, SimulatorParams, SmootherParams, SolveInfo,
+                   get_library, SE3MPC_MAX_SPHERES)
 
 INFO_DTYPE = np.dtype([("fun", "<f8"), ("nit", "<i4"), ("nfev", "<i4"), ("status", "<i4"), ("task", "<i4")])
 assert INFO_DTYPE.itemsize == 24
@@ -831,6 +831,87 @@ class Ops:
         if log:
             out.update(log_state=ls, log_cmd=lc, log_time=lt)
         return out
+
+    # ------------------------------------------------------------------ TrajectorySmoother (per-drone rows)
+    def smoother_state(self, B: int):
+        """Fresh smoother members for B drones (TrajectorySmoother.__init__): float64 (B, 25), all zero = no trajectory."""
+        st = self.be.empty((B, SMOOTHER_STATE_WORDS), "f64")
+        self.lib.smoother_reset(B, self.be.ptr(st), self.be.stream())
+        return st
+
+    def _smoother_record(self, state, B):
+        self.be.check(state, "smoother state")
+        if tuple(state.shape) != (B, SMOOTHER_STATE_WORDS) or self.be.suffix(state) != "f64":
+            raise ValueError(f"smoother state: float64 ({B}, {SMOOTHER_STATE_WORDS})")
+
+    def _clock(self, now, B, name="now"):
+        self.be.check(now, name)
+        if tuple(now.shape) != (B,) or self.be.suffix(now) != "f64":
+            raise ValueError(f"{name}: float64 ({B},)")
+
+    def _plan_ptrs(self, B, suf, timestamps, P, V, A, strides):
+        """The nine plan arguments (N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA) of the smoother's entry points."""
+        N, ts_stride, sP, sV, sA = self._plan_args(B, suf, timestamps, P, V, A, strides)
+        return [N, self.be.ptr(timestamps), ts_stride, self.be.ptr(P), sP, self.be.ptr(V), sV, self.be.ptr(A), sA]
+
+    def smoother_update(self, mp: SmootherParams, state, now, timestamps, P, V=None, A=None, strides=None, old=None, old_strides=None) -> None:
+        """update_trajectory for B drones at the clocks now float64 (B,): the new plan (timestamps, P, V, A[, strides]) as in :meth:`closed_loop`
+        (N = 0 rows allowed), `old` = None or the (timestamps, P, V, A) the drones have been following (read for drones that have a
+        trajectory).  `state` float64 (B, 25) is updated in place."""
+        B = now.shape[0]
+        self._clock(now, B)
+        self._smoother_record(state, B)
+        suf = self.be.suffix(P)
+        new_args = self._plan_ptrs(B, suf, timestamps, P, V, A, strides)
+        old_args = [0, 0, 0, 0, 0, 0, 0, 0, 0] if old is None else self._plan_ptrs(B, suf, old[0], old[1], old[2], old[3], old_strides)
+        self.lib.loop_call("smoother_update", suf, mp, B, self.be.ptr(now), *old_args, *new_args, self.be.ptr(state), self.be.stream())
+
+    def smoother_desired(self, mp: SmootherParams, state, now, pos, vel, timestamps, P, V=None, A=None, strides=None):
+        """get_desired_state for B drones at the clocks now float64 (B,): pos, vel (B, 3) the drones' own state, the current plan as in
+        :meth:`closed_loop` (N = 0 rows allowed).  `state` is updated in place.
+        -> dict(target (B, 9) = (position, velocity, acceleration), branch int32 (B,): 0 failsafe, 1 transition point, 2 transition just
+        completed, 3 normal following, 4 no trajectory)."""
+        B = now.shape[0]
+        self._clock(now, B)
+        self._smoother_record(state, B)
+        suf = self.be.suffix(pos)
+        self._rows3(pos, B, "pos", suf); self._rows3(vel, B, "vel", suf)
+        plan = self._plan_ptrs(B, suf, timestamps, P, V, A, strides)
+        target, branch = self.be.empty((B, 9), suf), self.be.empty((B,), "i32")
+        self.lib.loop_call("smoother_desired", suf, mp, B, self.be.ptr(now), self.be.ptr(pos), self.be.ptr(vel), *plan, self.be.ptr(state),
+                           self.be.ptr(target), self.be.ptr(branch), self.be.stream())
+        return dict(target=target, branch=branch)
+
+    def closed_loop_smoothed(self, mp: SmootherParams, cp: ControllerParams, sp: SimulatorParams, state, smoother_state, time, pos, vel, att,
+                             omega, timestamps, P, V=None, A=None, nsteps: int = 1, sim_dt: float = 0.01, strides=None, wind=None, gust=None,
+                             log: bool = False):
+        """`nsteps` x (get_desired_state -> compute_control -> DroneSimulator.step) for B drones in ONE launch: :meth:`closed_loop` with the
+        reference's TrajectorySmoother between plan and controller.  time, pos, vel, att, omega, `state` (B, 12) and `smoother_state`
+        (B, 25) are updated in place.  -> dict([log_state (nsteps, B, 12), log_cmd (nsteps, B, 4), log_time (nsteps, B), log_target
+        (nsteps, B, 9)])."""
+        B = time.shape[0]
+        suf = self.be.suffix(pos)
+        for a, nm in ((pos, "pos"), (vel, "vel"), (att, "att"), (omega, "omega")):
+            self._rows3(a, B, nm, suf)
+        self._clock(time, B, "time")
+        self._ctrl_state(state, B)
+        self._smoother_record(smoother_state, B)
+        plan = self._plan_ptrs(B, suf, timestamps, P, V, A, strides)
+        w_stride = self._wind(wind, B, suf)
+        gust_step, gust_vec = -1, None
+        if gust is not None:
+            gust_step = int(gust[0])
+            gust_vec = (_C.c_double * 3)(*[float(x) for x in gust[1]])
+        nsteps = int(nsteps)
+        ls = self.be.empty((nsteps, B, 12), suf) if log else None
+        lc = self.be.empty((nsteps, B, 4), suf) if log else None
+        lt = self.be.empty((nsteps, B), "f64") if log else None
+        lg = self.be.empty((nsteps, B, 9), suf) if log else None
+        self.lib.loop_call("closed_loop_smoothed", suf, mp, cp, sp, B, nsteps, float(sim_dt), *plan, self.be.ptr(time), self.be.ptr(pos),
+                           self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega), self.be.ptr(state), self.be.ptr(smoother_state),
+                           self.be.ptr(wind), w_stride, gust_step, gust_vec, self.be.ptr(ls), self.be.ptr(lc), self.be.ptr(lt), self.be.ptr(lg),
+                           self.be.stream())
+        return dict(log_state=ls, log_cmd=lc, log_time=lt, log_target=lg) if log else {}
 
     # ------------------------------------------------------------------ problem layout
     def solve(self, params: Params, p0, v0, goal, x0=None, want_trajectory=True, out=None):

@@ -624,6 +624,86 @@ int se3mpc_closed_loop_f64(const se3mpc_controller_params* cp, const se3mpc_simu
                            const double* gust_wind, int stop_at_plan_end, double* log_state, double* log_cmd, double* log_time,
                            int32_t* steps_taken, void* stream);
 
+/* ------------------------------------------------------------------ TrajectorySmoother
+ * The stage of the reference's edge loop between planner and controller (edge/main_improved.py:96-152; "smoother.py" =
+ * src/dart_planner/control/trajectory_smoother.py), one drone per lane, reproduced with its quirks: its own plan sampler (:215-278:
+ * stamps relative to timestamps[0], blend (1 - alpha) * row[i] + alpha * row[i + 1], an empty plan samples as zeros), the minimum-jerk
+ * transition (:280-319), the per-call limits (:64-92), the exponential filter that a filtered position at the exact origin bypasses
+ * (:94-113) and the decaying-velocity hover after `timeout` seconds without a plan (:321-338).  All clock arithmetic is double. */
+
+/* The class's constants (smoother.py:19-26, :151, :176-179, :101, :329-331). */
+typedef struct se3mpc_smoother_params {
+  double transition_time;                      /* s, > 0                                 (:19)                   */
+  double velocity_limit, acceleration_limit, jerk_limit;   /* (:24-26)                                           */
+  double update_dt;                            /* the fixed dt of get_desired_state, > 0 (:179)                  */
+  double smoothing_window;                     /* alpha = min(1, update_dt / window), > 0 (:101)                 */
+  double pos_diff_threshold, vel_diff_threshold;   /* a new plan further away starts a transition (:151)         */
+  double timeout;                              /* s without a plan before the failsafe   (:176, :331)            */
+  double decay_rate, decay_cap;                /* failsafe velocity decay, 1/s and s     (:329-331)              */
+} se3mpc_smoother_params;
+
+/* Mutable smoother members (smoother.py:28-46), SE3MPC_SMOOTHER_STATE_WORDS doubles per drone: [0..8] last_filtered_pos, _vel, _acc;
+ * [9..20] transition_start_pos, transition_start_vel, transition_target_pos, transition_target_vel; [21] transition_start_time;
+ * [22] last_cloud_update; [23] trajectory_start_time; [24] bit set: 1 current_trajectory is not None, 2 in_transition.
+ * The plan itself (current_trajectory) stays the caller's and is passed per call. */
+#define SE3MPC_SMOOTHER_STATE_WORDS 25
+
+int se3mpc_smoother_default_params(se3mpc_smoother_params* out);
+/* TrajectorySmoother.__init__ (smoother.py:28-46) for B drones: state = device double[B][25], all zero (no trajectory). */
+int se3mpc_smoother_reset(int B, double* state, void* stream);
+
+/* update_trajectory (smoother.py:115-165) for B drones at the clocks now [B] (where the reference reads time.time()).  Plans as in
+ * se3mpc_closed_loop_* (timestamps, P, V, A and their strides; V, A may be NULL = zeros), N_old / N_new >= 0 rows (0 = an empty plan,
+ * which samples as zeros; its pointers are not read).  The old plan is read only for drones that have a trajectory and may be NULL
+ * when none does (a drone that has one then samples zeros).  `state` is read and updated.
+ * Argument rules of the four entry points: a NULL required operand: SE3MPC_ERR_NULL; B < 0, nsteps < 0, a negative N or stride, N >
+ * 4096: SE3MPC_ERR_SHAPE; transition_time / update_dt / smoothing_window not finite or not positive, non-finite sim_dt:
+ * SE3MPC_ERR_PARAM (a limit or threshold may be infinite: it then never fires).  B = 0 and nsteps = 0 are no-ops.  Every rejected call sets se3mpc_last_error and launches nothing. */
+int se3mpc_smoother_update_f32(const se3mpc_smoother_params* mp, int B, const double* now, int N_old, const double* ts_old,
+                               long long ts_old_stride, const float* P_old, long long strideP_old, const float* V_old,
+                               long long strideV_old, const float* A_old, long long strideA_old, int N_new, const double* ts_new,
+                               long long ts_new_stride, const float* P_new, long long strideP_new, const float* V_new,
+                               long long strideV_new, const float* A_new, long long strideA_new, double* state, void* stream);
+int se3mpc_smoother_update_f64(const se3mpc_smoother_params* mp, int B, const double* now, int N_old, const double* ts_old,
+                               long long ts_old_stride, const double* P_old, long long strideP_old, const double* V_old,
+                               long long strideV_old, const double* A_old, long long strideA_old, int N_new, const double* ts_new,
+                               long long ts_new_stride, const double* P_new, long long strideP_new, const double* V_new,
+                               long long strideV_new, const double* A_new, long long strideA_new, double* state, void* stream);
+
+/* get_desired_state (smoother.py:167-213) for B drones at the clocks now [B]: pos, vel [B][3] = the drone's own state (the failsafe
+ * and the no-trajectory hover return it), the current plan of N >= 0 rows.  Outputs (any may be NULL): target [B][9] = (position,
+ * velocity, acceleration), branch int32 [B]: 0 failsafe, 1 transition point, 2 transition just completed (then normal following),
+ * 3 normal following, 4 no trajectory.  `state` is read and updated. */
+int se3mpc_smoother_desired_f32(const se3mpc_smoother_params* mp, int B, const double* now, const float* pos, const float* vel, int N,
+                                const double* timestamps, long long ts_stride, const float* P, long long strideP, const float* V,
+                                long long strideV, const float* A, long long strideA, double* state, float* target, int32_t* branch,
+                                void* stream);
+int se3mpc_smoother_desired_f64(const se3mpc_smoother_params* mp, int B, const double* now, const double* pos, const double* vel, int N,
+                                const double* timestamps, long long ts_stride, const double* P, long long strideP, const double* V,
+                                long long strideV, const double* A, long long strideA, double* state, double* target, int32_t* branch,
+                                void* stream);
+
+/* The control-rate part of the reference's edge loop between two plans (edge/main_improved.py:125-152), `nsteps` times per drone in ONE
+ * launch:  t = state.timestamp;  target = get_desired_state(t, state);  cmd = compute_control(state, target, yaw 0);  [step ==
+ * gust_step: the wind becomes gust_wind];  state = DroneSimulator.step(state, cmd, sim_dt).  Arguments as se3mpc_closed_loop_* (no
+ * stop_at_plan_end: the smoother holds the plan's last row, and no steps_taken: every drone takes nsteps), plus the smoother's
+ * parameters, its records smoother_state [B][25] (in / out) and log_target [nsteps][B][9] (NULL or the targets handed to the
+ * controller).  The same bits as nsteps chained se3mpc_smoother_desired_* -> se3mpc_control_* -> se3mpc_simulator_step_* launches. */
+int se3mpc_closed_loop_smoothed_f32(const se3mpc_smoother_params* mp, const se3mpc_controller_params* cp,
+                                    const se3mpc_simulator_params* sp, int B, int nsteps, double sim_dt, int N, const double* timestamps,
+                                    long long ts_stride, const float* P, long long strideP, const float* V, long long strideV,
+                                    const float* A, long long strideA, double* time, float* pos, float* vel, float* att, float* omega,
+                                    double* state, double* smoother_state, const float* wind, long long wind_stride, int gust_step,
+                                    const double* gust_wind, float* log_state, float* log_cmd, double* log_time, float* log_target,
+                                    void* stream);
+int se3mpc_closed_loop_smoothed_f64(const se3mpc_smoother_params* mp, const se3mpc_controller_params* cp,
+                                    const se3mpc_simulator_params* sp, int B, int nsteps, double sim_dt, int N, const double* timestamps,
+                                    long long ts_stride, const double* P, long long strideP, const double* V, long long strideV,
+                                    const double* A, long long strideA, double* time, double* pos, double* vel, double* att,
+                                    double* omega, double* state, double* smoother_state, const double* wind, long long wind_stride,
+                                    int gust_step, const double* gust_wind, double* log_state, double* log_cmd, double* log_time,
+                                    double* log_target, void* stream);
+
 /* The receding-horizon closed-loop Monte-Carlo of BASELINE config 5's named test shape (tests/test_monte_carlo_sim.py:24-72) in ONE
  * launch: for each of B drones, `cycles` times { se3mpc_solve_* from the drone's own (pos, vel) with the reference's cold start;
  * `substeps` x se3mpc_closed_loop_*'s step (plan sample -> compute_control -> DroneSimulator.step at sim_dt) against the fresh plan,

@@ -33,6 +33,42 @@ class ClosedLoopMonteCarlo:
             raise ValueError(f"{what} has no trajectory smoother (the one-launch kernels keep one plan per drone on the chip, DESIGN.md 5.7c): "
                              "use run / run_mppi with smoother=")
 
+    def _start(self, p0, v0, smoother=None):
+        """Every method's start: -> st (fresh controller records), sm (fresh smoother records, None without a smoother) and the drones'
+        flight state fl = (time, pos, vel, att, omega): zero clocks, clones of p0 / v0, zero attitudes and body rates."""
+        import torch
+        ops = self.ops
+        B = p0.shape[0]
+        pos, vel = p0.clone(), v0.clone()
+        att, om = torch.zeros_like(p0), torch.zeros_like(p0)
+        time = torch.zeros(B, dtype=torch.float64, device=ops.be.device)
+        st = ops.controller_state(self.controller, B)
+        return st, (ops.smoother_state(B) if smoother is not None else None), (time, pos, vel, att, om)
+
+    def _actor(self, smoother, st, sm, fl, strides, substeps: int, sim_dt: float, wind):
+        """-> act(plan, log): `substeps` control + simulator steps of every drone against plan = (stamps, P, V, A) with `strides`, as one
+        ``se3mpc_closed_loop_*`` launch -- or, with a smoother, update_trajectory against the plan of the call before (None at first; the
+        caller keeps that plan's tensors alive and unchanged until then) and one ``se3mpc_closed_loop_smoothed_*`` launch."""
+        ops, old = self.ops, [None]
+
+        def act(plan, log: bool = False):
+            if smoother is None:
+                return ops.closed_loop(self.controller, self.simulator, st, *fl, *plan, nsteps=substeps, sim_dt=sim_dt, strides=strides, wind=wind,
+                                       stop_at_plan_end=False, log=log)
+            ops.smoother_update(smoother, sm, fl[0], *plan, strides=strides, old=old[0], old_strides=strides)   # the wall clock of update_trajectory = the drones' clocks
+            old[0] = plan
+            return ops.closed_loop_smoothed(smoother, self.controller, self.simulator, st, sm, *fl, *plan, nsteps=substeps, sim_dt=sim_dt,
+                                            strides=strides, wind=wind, log=log)
+        return act
+
+    @staticmethod
+    def _result(st, sm, fl, **more):
+        time, pos, vel, att, om = fl
+        res = dict(pos=pos, vel=vel, att=att, omega=om, time=time, controller_state=st, **more)
+        if sm is not None:
+            res["smoother_state"] = sm
+        return res
+
     def run(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, wind=None, log: bool = False,
             smoother: Optional[SmootherParams] = None):
         """p0, v0, goal: (B, 3) device tensors (float32 or float64: the precision of the whole loop); wind: None, (3,) or (B, 3) newtons.
@@ -41,73 +77,37 @@ class ClosedLoopMonteCarlo:
         get_desired_state.  -> dict(pos, vel, att, omega (B, 3), time (B,), controller_state (B, 12), logs = [(solve outputs, closed-loop
         outputs)] if log[, smoother_state (B, 25)])."""
         import torch
-        if smoother is not None:
-            return self._run_smoothed(smoother, p0, v0, goal, cycles, substeps, sim_dt, wind, log)
         ops, prm = self.ops, self.params
-        dev = ops.be.device
-        B, N = p0.shape[0], prm.horizon
-        pos, vel = p0.clone(), v0.clone()
-        att, om = torch.zeros_like(p0), torch.zeros_like(p0)
-        time = torch.zeros(B, dtype=torch.float64, device=dev)
-        st = ops.controller_state(self.controller, B)
-        k = torch.arange(N, dtype=torch.float64, device=dev)
+        N = prm.horizon
+        st, sm, fl = self._start(p0, v0, smoother)
+        act = self._actor(smoother, st, sm, fl, (9 * N, 9 * N, 3 * N), substeps, sim_dt, wind)
+        k = torch.arange(N, dtype=torch.float64, device=ops.be.device)
         logs = []
-        sol = None
+        # without logs every cycle writes the same plan tensors again (the closed-loop launch of a cycle is ordered before the next solve); a
+        # smoother still reads the previous cycle's plan, so two sets alternate
+        sols = [None] if smoother is None else [None, None]
         for c in range(cycles):
-            # without logs every cycle writes the same plan tensors again (the closed-loop launch of a cycle is ordered before the next solve)
-            sol = ops.solve(prm, pos, vel, goal, want_trajectory=True if log else "accelerations", out=None if log else sol)
-            stamps = (c * substeps * sim_dt) + k * prm.dt
+            slot = c % len(sols)
+            sol = sols[slot] = ops.solve(prm, fl[1], fl[2], goal, want_trajectory=True if log else "accelerations", out=None if log else sols[slot])
             X = sol["x"]
-            out = ops.closed_loop(self.controller, self.simulator, st, time, pos, vel, att, om, stamps, X, X[:, 3 * N:], sol["accelerations"],
-                                  nsteps=substeps, sim_dt=sim_dt, strides=(9 * N, 9 * N, 3 * N), wind=wind, stop_at_plan_end=False, log=log)
+            out = act(((c * substeps * sim_dt) + k * prm.dt, X, X[:, 3 * N:], sol["accelerations"]), log)
             if log:
                 logs.append((sol, out))
-        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, controller_state=st, logs=logs)
-
-    def _run_smoothed(self, smoother, p0, v0, goal, cycles, substeps, sim_dt, wind, log):
-        import torch
-        ops, prm = self.ops, self.params
-        dev = ops.be.device
-        B, N = p0.shape[0], prm.horizon
-        pos, vel = p0.clone(), v0.clone()
-        att, om = torch.zeros_like(p0), torch.zeros_like(p0)
-        time = torch.zeros(B, dtype=torch.float64, device=dev)
-        st, sm = ops.controller_state(self.controller, B), ops.smoother_state(B)
-        k = torch.arange(N, dtype=torch.float64, device=dev)
-        strides = (9 * N, 9 * N, 3 * N)
-        logs, sols, old = [], [None, None], None
-        for c in range(cycles):
-            sol = ops.solve(prm, pos, vel, goal, want_trajectory=True if log else "accelerations", out=None if log else sols[c % 2])
-            sols[c % 2] = sol
-            X = sol["x"]
-            new = ((c * substeps * sim_dt) + k * prm.dt, X, X[:, 3 * N:], sol["accelerations"])
-            ops.smoother_update(smoother, sm, time, *new, strides=strides, old=old, old_strides=strides)      # the wall clock of update_trajectory = the drones' clocks
-            out = ops.closed_loop_smoothed(smoother, self.controller, self.simulator, st, sm, time, pos, vel, att, om, *new, nsteps=substeps,
-                                           sim_dt=sim_dt, strides=strides, wind=wind, log=log)
-            old = new
-            if log:
-                logs.append((sol, out))
-        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, controller_state=st, logs=logs, smoother_state=sm)
+        return self._result(st, sm, fl, logs=logs)
 
     def run_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, wind=None, want_last_plan: bool = False, smoother=None):
         """The same Monte-Carlo in ONE launch (``se3mpc_monte_carlo_*``: every cycle's solve and control / simulator steps inside one kernel,
         each drone paying only for its own slow solves instead of waiting, 2 x `cycles` times, at a kernel boundary for the slowest drone of
         the batch).  Same code, same bits as :meth:`run`.  One host synchronise at the end reads the overflow counter; if a solve needed more
         L-BFGS memory than the launch's LDS image holds (never with the reference's options) the run is repeated by :meth:`run`."""
-        import torch
         self._no_smoother(smoother, "run_fused")
         ops = self.ops
-        dev = ops.be.device
-        B = p0.shape[0]
-        pos, vel = p0.clone(), v0.clone()
-        att, om = torch.zeros_like(p0), torch.zeros_like(p0)
-        time = torch.zeros(B, dtype=torch.float64, device=dev)
-        st = ops.controller_state(self.controller, B)
-        out = ops.monte_carlo(self.params, self.controller, self.simulator, st, time, pos, vel, att, om, goal, cycles, substeps, sim_dt, wind=wind,
+        st, sm, fl = self._start(p0, v0)
+        out = ops.monte_carlo(self.params, self.controller, self.simulator, st, *fl, goal, cycles, substeps, sim_dt, wind=wind,
                               want_last_plan=want_last_plan)
         if int(ops.be.to_host(out["overflowed"])[0]) != 0:
             return self.run(p0, v0, goal, cycles, substeps, sim_dt, wind=wind)
-        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, controller_state=st, logs=[], last_plan=out if want_last_plan else None)
+        return self._result(st, sm, fl, logs=[], last_plan=out if want_last_plan else None)
 
     def resolve_shift(self, substeps: int, sim_dt: float, shift: Optional[int] = None) -> int:
         """Rows the MPPI nominal moves forward per planning cycle.  None: the plan steps one act phase covers, rounded half up,
@@ -117,20 +117,15 @@ class ClosedLoopMonteCarlo:
             shift = int(math.floor(substeps * sim_dt / self.params.dt + 0.5))
         return max(0, min(N, int(shift)))
 
-    def _mppi_start(self, p0, v0, nominal):
+    def _mppi_start(self, p0, nominal):
+        """The MPPI nominal the run starts from: a clone of `nominal`, or hover."""
         import torch
-        ops, prm = self.ops, self.params
-        B, N = p0.shape[0], prm.horizon
-        pos, vel = p0.clone(), v0.clone()
-        att, om = torch.zeros_like(p0), torch.zeros_like(p0)
-        time = torch.zeros(B, dtype=torch.float64, device=ops.be.device)
-        st = ops.controller_state(self.controller, B)
-        if nominal is None:
-            U = torch.zeros(B, N, 3, dtype=p0.dtype, device=ops.be.device)
-            U[:, :, 2] = prm.mass * prm.gravity
-        else:
-            U = nominal.clone()
-        return pos, vel, att, om, time, st, U
+        if nominal is not None:
+            return nominal.clone()
+        prm = self.params
+        U = torch.zeros(p0.shape[0], prm.horizon, 3, dtype=p0.dtype, device=self.ops.be.device)
+        U[:, :, 2] = prm.mass * prm.gravity
+        return U
 
     def run_mppi(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
                  seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None, nominal=None,
@@ -148,50 +143,29 @@ class ClosedLoopMonteCarlo:
         (``se3mpc_mppi_closed_loop_*`` with no simulator steps), update_trajectory against the previous cycle's plan and `substeps` steps of
         ``se3mpc_closed_loop_smoothed_*``; clearance is None (only the fused act phase measures it), smoother_state (B, 25) is added."""
         import torch
-        ops = self.ops
-        pos, vel, att, om, time, st, U = self._mppi_start(p0, v0, nominal)
+        ops, prm = self.ops, self.params
+        B, N = p0.shape[0], prm.horizon
+        smoothed = smoother is not None
+        st, sm, fl = self._start(p0, v0, smoother)
+        U = self._mppi_start(p0, nominal)
         sh = self.resolve_shift(substeps, sim_dt, shift)
-        if smoother is not None:
-            return self._run_mppi_smoothed(smoother, pos, vel, att, om, time, st, U, sh, goal, cycles, substeps, sim_dt, n_samples, iters, sigma,
-                                           temperature, seed, spheres, obstacle_weight, wind, log)
+        act = self._actor(smoother, st, sm, fl, (9 * N, 9 * N, 9 * N), substeps, sim_dt, wind)
+        k = torch.arange(N, dtype=torch.float64, device=ops.be.device) if smoothed else None
         logs, traces, out, clr = [], [], None, None
         for c in range(cycles):
-            out = ops.mppi_closed_loop(self.params, self.controller, self.simulator, st, time, pos, vel, att, om, goal, U, 1, substeps, sim_dt,
-                                       n_samples, iters, sigma, temperature, seed=seed, cycle_base=c, shift=sh, spheres=spheres,
-                                       obstacle_weight=obstacle_weight, wind=wind, want_plan=log, clearance=clr)
+            # without a smoother the kernel flies the act phase itself; with one it only plans, and every cycle's plan is a tensor of its own
+            out = ops.mppi_closed_loop(prm, self.controller, self.simulator, st, *fl, goal, U, 1, 0 if smoothed else substeps, sim_dt, n_samples, iters,
+                                       sigma, temperature, seed=seed, cycle_base=c, shift=sh, spheres=spheres, obstacle_weight=obstacle_weight, wind=wind,
+                                       want_plan=log or smoothed, clearance=clr, want_clearance=not smoothed)
             clr = out["clearance"]
             traces.append(out["trace"])
+            if smoothed:
+                flat = out["plan_last"].view(B, 9 * N)            # (P, V, A) of drone b: 3N values each, 9N apart from drone to drone
+                act(((c * substeps * sim_dt) + k * prm.dt, flat, flat[:, 3 * N:], flat[:, 6 * N:]))
             if log:
                 logs.append(dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"]))
-        trace = torch.cat(traces, dim=1) if traces else torch.zeros(p0.shape[0], 0, max(int(iters), 0), dtype=p0.dtype, device=ops.be.device)
-        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, controller_state=st, logs=logs, U=U, cost=None if out is None else out["cost"],
-                    trace=trace, clearance=clr)
-
-    def _run_mppi_smoothed(self, smoother, pos, vel, att, om, time, st, U, sh, goal, cycles, substeps, sim_dt, n_samples, iters, sigma, temperature,
-                           seed, spheres, obstacle_weight, wind, log):
-        import torch
-        ops, prm = self.ops, self.params
-        B, N = pos.shape[0], prm.horizon
-        sm = ops.smoother_state(B)
-        k = torch.arange(N, dtype=torch.float64, device=ops.be.device)
-        strides = (9 * N, 9 * N, 9 * N)
-        logs, traces, out, old = [], [], None, None
-        for c in range(cycles):
-            out = ops.mppi_closed_loop(prm, self.controller, self.simulator, st, time, pos, vel, att, om, goal, U, 1, 0, sim_dt, n_samples, iters, sigma,
-                                       temperature, seed=seed, cycle_base=c, shift=sh, spheres=spheres, obstacle_weight=obstacle_weight, wind=wind,
-                                       want_plan=True, want_clearance=False)
-            traces.append(out["trace"])
-            flat = out["plan_last"].view(B, 9 * N)                # (P, V, A) of drone b: 3N values each, 9N apart from drone to drone
-            new = ((c * substeps * sim_dt) + k * prm.dt, flat, flat[:, 3 * N:], flat[:, 6 * N:])
-            ops.smoother_update(smoother, sm, time, *new, strides=strides, old=old, old_strides=strides)
-            ops.closed_loop_smoothed(smoother, self.controller, self.simulator, st, sm, time, pos, vel, att, om, *new, nsteps=substeps, sim_dt=sim_dt,
-                                     strides=strides, wind=wind)
-            old = new
-            if log:
-                logs.append(dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"]))
-        trace = torch.cat(traces, dim=1) if traces else torch.zeros(B, 0, max(int(iters), 0), dtype=pos.dtype, device=ops.be.device)
-        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, controller_state=st, logs=logs, U=U, cost=None if out is None else out["cost"],
-                    trace=trace, clearance=None, smoother_state=sm)
+        trace = torch.cat(traces, dim=1) if traces else torch.zeros(B, 0, max(int(iters), 0), dtype=p0.dtype, device=ops.be.device)
+        return self._result(st, sm, fl, logs=logs, U=U, cost=None if out is None else out["cost"], trace=trace, clearance=clr)
 
     def run_mppi_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float,
                        temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None,
@@ -206,15 +180,14 @@ class ClosedLoopMonteCarlo:
         (float32) / two (float64) wavefronts per SIMD instead of four, and one lane per workgroup flies while the others wait): for thousands of
         drones drive the chain (``tools/gpu_probe_mppi_closed_loop.py``, ``chain_form``) unless the clearance output is what you need."""
         self._no_smoother(smoother, "run_mppi_fused")
-        ops = self.ops
-        pos, vel, att, om, time, st, U = self._mppi_start(p0, v0, nominal)
+        st, sm, fl = self._start(p0, v0)
+        U = self._mppi_start(p0, nominal)
         sh = self.resolve_shift(substeps, sim_dt, shift)
-        out = ops.mppi_closed_loop(self.params, self.controller, self.simulator, st, time, pos, vel, att, om, goal, U, cycles, substeps, sim_dt,
-                                   n_samples, iters, sigma, temperature, seed=seed, cycle_base=0, shift=sh, spheres=spheres,
-                                   obstacle_weight=obstacle_weight, wind=wind, want_plan=log)
+        out = self.ops.mppi_closed_loop(self.params, self.controller, self.simulator, st, *fl, goal, U, cycles, substeps, sim_dt,
+                                        n_samples, iters, sigma, temperature, seed=seed, cycle_base=0, shift=sh, spheres=spheres,
+                                        obstacle_weight=obstacle_weight, wind=wind, want_plan=log)
         logs = [dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"])] if log else []
-        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, controller_state=st, logs=logs, U=U, cost=out["cost"], trace=out["trace"],
-                    clearance=out["clearance"])
+        return self._result(st, sm, fl, logs=logs, U=U, cost=out["cost"], trace=out["trace"], clearance=out["clearance"])
 
     def capture(self, B: int, dtype, cycles: int, substeps: int, sim_dt: float, with_wind: bool = True, smoother=None):
         """The whole Monte-Carlo (2 x `cycles` kernel launches + the plan stamps) captured ONCE into a hipGraph; each call of the

@@ -32,33 +32,32 @@ control_kernel(CtrlDev<R> c, int B, const double* __restrict__ time, const R* __
                const R* __restrict__ att, const R* __restrict__ omega, const R* __restrict__ dpos, const R* __restrict__ dvel,
                const R* __restrict__ dacc, const R* __restrict__ yaw, const R* __restrict__ yaw_rate, double* __restrict__ state,
                R* __restrict__ thrust, R* __restrict__ torque, R* __restrict__ body_thrust, R* __restrict__ body_rates,
-               int32_t* __restrict__ flags, const double* __restrict__ sample_time, int N, const double* __restrict__ timestamps,
-               long long ts_stride, const R* __restrict__ P, long long strideP, const R* __restrict__ V, long long strideV,
-               const R* __restrict__ A, long long strideA, R* __restrict__ target) {
+               int32_t* __restrict__ flags, const double* __restrict__ sample_time, PlanView<R> plan, R* __restrict__ target) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   CtrlRegs<R> s = load_ctrl<R>(state + (size_t)b * SE3MPC_CONTROLLER_STATE_WORDS);
-  R p[3], v[3], a[3], w[3], dp[3], dv[3], da[3];
-  for (int i = 0; i < 3; ++i) { p[i] = pos[3 * b + i]; v[i] = vel[3 * b + i]; a[i] = att[3 * b + i]; w[i] = omega[3 * b + i]; }
+  DroneRegs<R> d;
+  d.load_state(b, pos, vel, att, omega);
+  R dp[3], dv[3], da[3];
   if (sample_time != nullptr) {                       // compute_control_from_trajectory: the target is the plan sampled at sample_time
+    const PlanView<R> rows = plan.of(b);
     PlanCursor<R> cur;
     cursor_reset(cur);
-    sample_plan<R>(sample_time[b], N, timestamps + (size_t)b * ts_stride, P + (size_t)b * strideP,
-                   V != nullptr ? V + (size_t)b * strideV : nullptr, A != nullptr ? A + (size_t)b * strideA : nullptr, dp, dv, da, cur);
+    sample_plan<R>(sample_time[b], plan.N, rows.ts, rows.P, rows.V, rows.A, dp, dv, da, cur);   // (its parameters are __restrict__)
     if (target != nullptr) for (int i = 0; i < 3; ++i) { target[9 * b + i] = dp[i]; target[9 * b + 3 + i] = dv[i]; target[9 * b + 6 + i] = da[i]; }
   } else {
     for (int i = 0; i < 3; ++i) { dp[i] = dpos[3 * b + i]; dv[i] = dvel[3 * b + i]; da[i] = dacc != nullptr ? dacc[3 * b + i] : (R)0; }
   }
   R th, tq[3];
   int fl;
-  control_step<R>(c, s, time[b], p, v, a, w, dp, dv, da, yaw != nullptr ? yaw[b] : (R)0, yaw_rate != nullptr ? yaw_rate[b] : (R)0, th, tq, fl);
+  control_step<R>(c, s, time[b], d.p, d.v, d.a, d.w, dp, dv, da, yaw != nullptr ? yaw[b] : (R)0, yaw_rate != nullptr ? yaw_rate[b] : (R)0, th, tq, fl);
   store_ctrl<R>(state + (size_t)b * SE3MPC_CONTROLLER_STATE_WORDS, s);
   if (thrust != nullptr) thrust[b] = th;
   if (torque != nullptr) for (int i = 0; i < 3; ++i) torque[3 * b + i] = tq[i];
   if (body_thrust != nullptr) body_thrust[b] = fmin(fmax(th / c.max_thrust, (R)0), (R)1);   // controller.py:721
   if (body_rates != nullptr) {
     const R inr[3] = {(R)0.1, (R)0.1, (R)0.2};                                    // controller.py:717 (its own inertia, not the config's)
-    for (int i = 0; i < 3; ++i) body_rates[3 * b + i] = w[i] + (tq[i] / inr[i]) * (R)0.001;   // :718-720
+    for (int i = 0; i < 3; ++i) body_rates[3 * b + i] = d.w[i] + (tq[i] / inr[i]) * (R)0.001;   // :718-720
   }
   if (flags != nullptr) flags[b] = fl;
 }
@@ -73,14 +72,13 @@ control_fast_kernel(CtrlDev<R> c, FastDev<R> f, int B, double dt, const R* __res
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   CtrlRegs<R> s = load_ctrl<R>(state + (size_t)b * SE3MPC_CONTROLLER_STATE_WORDS);
-  R p[3], v[3], a[3], w[3], dp[3], dv[3], da[3];
-  for (int i = 0; i < 3; ++i) {
-    p[i] = pos[3 * b + i]; v[i] = vel[3 * b + i]; a[i] = att[3 * b + i]; w[i] = omega[3 * b + i];
-    dp[i] = dpos[3 * b + i]; dv[i] = dvel[3 * b + i]; da[i] = dacc != nullptr ? dacc[3 * b + i] : (R)0;
-  }
+  DroneRegs<R> d;
+  d.load_state(b, pos, vel, att, omega);
+  R dp[3], dv[3], da[3];
+  for (int i = 0; i < 3; ++i) { dp[i] = dpos[3 * b + i]; dv[i] = dvel[3 * b + i]; da[i] = dacc != nullptr ? dacc[3 * b + i] : (R)0; }
   R th, tq[3];
   int fl;
-  control_step_fast<R>(c, f, s, dt, p, v, a, w, dp, dv, da, yaw != nullptr ? yaw[b] : (R)0, yaw_rate != nullptr ? yaw_rate[b] : (R)0, th, tq, fl);
+  control_step_fast<R>(c, f, s, dt, d.p, d.v, d.a, d.w, dp, dv, da, yaw != nullptr ? yaw[b] : (R)0, yaw_rate != nullptr ? yaw_rate[b] : (R)0, th, tq, fl);
   store_ctrl<R>(state + (size_t)b * SE3MPC_CONTROLLER_STATE_WORDS, s);
   if (thrust != nullptr) thrust[b] = th;
   if (torque != nullptr) for (int i = 0; i < 3; ++i) torque[3 * b + i] = tq[i];
@@ -151,51 +149,27 @@ desired_frame_kernel(CtrlDev<R> c, int B, int method, const R* __restrict__ yaw_
 // ---- the closed loop: nsteps x (sample, control, simulate) per drone in one launch
 template <typename R>
 __global__ void __launch_bounds__(64)
-closed_loop_kernel(CtrlDev<R> c, SimDev<R> m, int B, int nsteps, double sim_dt, int N, const double* __restrict__ timestamps,
-                   long long ts_stride, const R* __restrict__ P, long long strideP, const R* __restrict__ V, long long strideV,
-                   const R* __restrict__ A, long long strideA, double* __restrict__ time, R* __restrict__ pos, R* __restrict__ vel,
-                   R* __restrict__ att, R* __restrict__ omega, double* __restrict__ state, const R* __restrict__ wind,
-                   long long wind_stride, int gust_step, R gx, R gy, R gz, int stop_at_plan_end, R* __restrict__ log_state,
-                   R* __restrict__ log_cmd, double* __restrict__ log_time, int32_t* __restrict__ steps_taken) {
+closed_loop_kernel(CtrlDev<R> c, SimDev<R> m, int B, int nsteps, double sim_dt, PlanView<R> plan, double* __restrict__ time,
+                   R* __restrict__ pos, R* __restrict__ vel, R* __restrict__ att, R* __restrict__ omega, double* __restrict__ state,
+                   const R* __restrict__ wind, long long wind_stride, int gust_step, R gx, R gy, R gz, int stop_at_plan_end,
+                   R* __restrict__ log_state, R* __restrict__ log_cmd, double* __restrict__ log_time, int32_t* __restrict__ steps_taken) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   CtrlRegs<R> s = load_ctrl<R>(state + (size_t)b * SE3MPC_CONTROLLER_STATE_WORDS);
-  R p[3], v[3], a[3], w[3], wd[3] = {(R)0, (R)0, (R)0};
-  for (int i = 0; i < 3; ++i) {
-    p[i] = pos[3 * b + i]; v[i] = vel[3 * b + i]; a[i] = att[3 * b + i]; w[i] = omega[3 * b + i];
-    if (wind != nullptr) wd[i] = wind[(size_t)b * wind_stride + i];
-  }
-  double t = time[b];
-  const double* ts = timestamps + (size_t)b * ts_stride;
-  const R* Pb = P + (size_t)b * strideP;
-  const R* Vb = V != nullptr ? V + (size_t)b * strideV : nullptr;
-  const R* Ab = A != nullptr ? A + (size_t)b * strideA : nullptr;
-  const double ts_last = ts[N - 1];
+  DroneRegs<R> d;
+  d.load(b, pos, vel, att, omega, wind, wind_stride, time);
+  const int N = plan.N;
+  const PlanView<R> rows = plan.of(b);
+  const double* __restrict__ ts = rows.ts;
+  const R* __restrict__ Pb = rows.P;
+  const R* __restrict__ Vb = rows.V;
+  const R* __restrict__ Ab = rows.A;
   const R dt = (R)sim_dt;
-  int taken = 0;
-  bool active = true;
   PlanCursor<R> cur;
   cursor_reset(cur);
-  for (int step = 0; step < nsteps; ++step) {
-    if (stop_at_plan_end && t > ts_last) active = false;                          // contract tests :130-131 / :263-264 (`break`)
-    if (log_state != nullptr) {
-      R* ls = log_state + ((size_t)step * B + b) * 12;
-      for (int i = 0; i < 3; ++i) { ls[i] = p[i]; ls[3 + i] = v[i]; ls[6 + i] = a[i]; ls[9 + i] = w[i]; }
-    }
-    if (log_time != nullptr) log_time[(size_t)step * B + b] = t;
-    R th = (R)NAN, tq[3] = {(R)NAN, (R)NAN, (R)NAN};
-    if (active) {
-      if (step == gust_step) { wd[0] = gx; wd[1] = gy; wd[2] = gz; }              // the gust of contract test :293-296 (the controller does not see the wind)
-      flight_step<R>(c, m, s, cur, N, ts, Pb, Vb, Ab, p, v, a, w, t, dt, sim_dt, wd, th, tq);
-      ++taken;
-    }
-    if (log_cmd != nullptr) {
-      R* lc = log_cmd + ((size_t)step * B + b) * 4;
-      lc[0] = th; lc[1] = tq[0]; lc[2] = tq[1]; lc[3] = tq[2];
-    }
-  }
-  for (int i = 0; i < 3; ++i) { pos[3 * b + i] = p[i]; vel[3 * b + i] = v[i]; att[3 * b + i] = a[i]; omega[3 * b + i] = w[i]; }
-  time[b] = t;
+  const int taken = lane_loop<R>(d, b, B, nsteps, gust_step, gx, gy, gz, stop_at_plan_end != 0, ts[N - 1], log_state, log_cmd, log_time,
+                                 [&](int, R& th, R* tq) { flight_step<R>(c, m, s, cur, N, ts, Pb, Vb, Ab, d.p, d.v, d.a, d.w, d.t, dt, sim_dt, d.wd, th, tq); });
+  d.store(b, pos, vel, att, omega, time);
   store_ctrl<R>(state + (size_t)b * SE3MPC_CONTROLLER_STATE_WORDS, s);
   if (steps_taken != nullptr) steps_taken[b] = taken;
 }
@@ -208,15 +182,11 @@ simulator_step_kernel(SimDev<R> m, int B, double dt_d, const R* __restrict__ thr
                       R* __restrict__ omega) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  R p[3], v[3], a[3], w[3], tq[3], wd[3];
-  for (int i = 0; i < 3; ++i) {
-    p[i] = pos[3 * b + i]; v[i] = vel[3 * b + i]; a[i] = att[3 * b + i]; w[i] = omega[3 * b + i]; tq[i] = torque[3 * b + i];
-    wd[i] = wind != nullptr ? wind[(size_t)b * wind_stride + i] : (R)0;
-  }
-  double t = time[b];
-  simulator_step<R>(m, p, v, a, w, t, thrust[b], tq, (R)dt_d, dt_d, wd);
-  for (int i = 0; i < 3; ++i) { pos[3 * b + i] = p[i]; vel[3 * b + i] = v[i]; att[3 * b + i] = a[i]; omega[3 * b + i] = w[i]; }
-  time[b] = t;
+  DroneRegs<R> d;
+  d.load(b, pos, vel, att, omega, wind, wind_stride, time);
+  const R tq[3] = {torque[3 * b], torque[3 * b + 1], torque[3 * b + 2]};
+  simulator_step<R>(m, d.p, d.v, d.a, d.w, d.t, thrust[b], tq, (R)dt_d, dt_d, d.wd);
+  d.store(b, pos, vel, att, omega, time);
 }
 
 __global__ void __launch_bounds__(64)
@@ -240,8 +210,7 @@ int control_impl(const se3mpc_controller_params* cp, int B, const double* time, 
   if (!time || !pos || !vel || !att || !omega || !dpos || !dvel || !state) return SE3MPC_ERR_NULL;
   hipLaunchKernelGGL(control_kernel<R>, dim3(grid_for(B, 64)), dim3(64), 0, (hipStream_t)stream, make_ctrl_dev<R>(*cp), B, time, pos, vel,
                      att, omega, dpos, dvel, dacc, yaw, yaw_rate, state, thrust, torque, body_thrust, body_rates, flags,
-                     (const double*)nullptr, 0, (const double*)nullptr, 0LL, (const R*)nullptr, 0LL, (const R*)nullptr, 0LL, (const R*)nullptr, 0LL,
-                     (R*)nullptr);
+                     (const double*)nullptr, PlanView<R>{}, (R*)nullptr);
   return launch_status("se3mpc_control");
 }
 
@@ -312,17 +281,16 @@ int desired_frame_impl(const se3mpc_controller_params* cp, int B, int method, co
 
 template <typename R>
 int control_plan_impl(const se3mpc_controller_params* cp, int B, const double* time, const double* sample_time, const R* pos, const R* vel,
-                      const R* att, const R* omega, int N, const double* timestamps, long long ts_stride, const R* P, long long strideP,
-                      const R* V, long long strideV, const R* A, long long strideA, double* state, R* thrust, R* torque, R* body_thrust,
+                      const R* att, const R* omega, const PlanView<R>& plan, double* state, R* thrust, R* torque, R* body_thrust,
                       R* body_rates, int32_t* flags, R* target, void* stream) {
   int rc = check_controller_params(cp);
   if (rc) return rc;
-  if (B < 0 || N < 1 || N > 4096 || ts_stride < 0 || strideP < 0 || strideV < 0 || strideA < 0) return SE3MPC_ERR_SHAPE;
+  if (B < 0 || !plan_shape_ok(plan, 1)) return SE3MPC_ERR_SHAPE;
   if (B == 0) return SE3MPC_OK;
-  if (!time || !sample_time || !pos || !vel || !att || !omega || !timestamps || !P || !state) return SE3MPC_ERR_NULL;
+  if (!time || !sample_time || !pos || !vel || !att || !omega || !plan_present(plan) || !state) return SE3MPC_ERR_NULL;
   hipLaunchKernelGGL(control_kernel<R>, dim3(grid_for(B, 64)), dim3(64), 0, (hipStream_t)stream, make_ctrl_dev<R>(*cp), B, time, pos, vel,
                      att, omega, (const R*)nullptr, (const R*)nullptr, (const R*)nullptr, (const R*)nullptr, (const R*)nullptr, state, thrust,
-                     torque, body_thrust, body_rates, flags, sample_time, N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA, target);
+                     torque, body_thrust, body_rates, flags, sample_time, plan, target);
   return launch_status("se3mpc_control_plan");
 }
 
@@ -341,9 +309,8 @@ int simulator_step_impl(const se3mpc_simulator_params* sp, int B, double dt, con
 }
 
 template <typename R>
-int closed_loop_impl(const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B, int nsteps, double sim_dt, int N,
-                     const double* timestamps, long long ts_stride, const R* P, long long strideP, const R* V, long long strideV,
-                     const R* A, long long strideA, double* time, R* pos, R* vel, R* att, R* omega, double* state, const R* wind,
+int closed_loop_impl(const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B, int nsteps, double sim_dt,
+                     const PlanView<R>& plan, double* time, R* pos, R* vel, R* att, R* omega, double* state, const R* wind,
                      long long wind_stride, int gust_step, const double* gust_wind, int stop_at_plan_end, R* log_state, R* log_cmd,
                      double* log_time, int32_t* steps_taken, void* stream) {
   int rc = check_controller_params(cp);
@@ -351,13 +318,12 @@ int closed_loop_impl(const se3mpc_controller_params* cp, const se3mpc_simulator_
   rc = check_simulator_params(sp);
   if (rc) return rc;
   if (!std::isfinite(sim_dt)) return SE3MPC_ERR_PARAM;
-  if (B < 0 || nsteps < 0 || N < 1 || N > 4096 || ts_stride < 0 || strideP < 0 || strideV < 0 || strideA < 0 || wind_stride < 0)
-    return SE3MPC_ERR_SHAPE;
+  if (B < 0 || nsteps < 0 || !plan_shape_ok(plan, 1) || wind_stride < 0) return SE3MPC_ERR_SHAPE;
   if (B == 0 || nsteps == 0) return SE3MPC_OK;
-  if (!timestamps || !P || !time || !pos || !vel || !att || !omega || !state || (gust_step >= 0 && !gust_wind)) return SE3MPC_ERR_NULL;
+  if (!plan_present(plan) || !time || !pos || !vel || !att || !omega || !state || (gust_step >= 0 && !gust_wind)) return SE3MPC_ERR_NULL;
   const R gx = gust_step >= 0 ? (R)gust_wind[0] : (R)0, gy = gust_step >= 0 ? (R)gust_wind[1] : (R)0, gz = gust_step >= 0 ? (R)gust_wind[2] : (R)0;
   hipLaunchKernelGGL(closed_loop_kernel<R>, dim3(grid_for(B, 64)), dim3(64), 0, (hipStream_t)stream, make_ctrl_dev<R>(*cp), make_sim_dev<R>(*sp),
-                     B, nsteps, sim_dt, N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA, time, pos, vel, att, omega, state, wind,
+                     B, nsteps, sim_dt, plan, time, pos, vel, att, omega, state, wind,
                      wind_stride, gust_step, gx, gy, gz, stop_at_plan_end, log_state, log_cmd, log_time, steps_taken);
   return launch_status("se3mpc_closed_loop");
 }
@@ -428,8 +394,9 @@ extern "C" int se3mpc_controller_reset(const se3mpc_controller_params* cp, int B
                                            long long ts_stride, const R* P, long long strideP, const R* V, long long strideV,   \
                                            const R* A, long long strideA, double* state, R* thrust, R* torque, R* body_thrust,  \
                                            R* body_rates, int32_t* flags, R* target, void* stream) {                           \
-    return control_plan_impl<R>(cp, B, time, sample_time, pos, vel, att, omega, N, timestamps, ts_stride, P, strideP, V, strideV, A, \
-                                strideA, state, thrust, torque, body_thrust, body_rates, flags, target, stream);               \
+    return control_plan_impl<R>(cp, B, time, sample_time, pos, vel, att, omega,                                               \
+                                PlanView<R>{N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA}, state, thrust, torque, \
+                                body_thrust, body_rates, flags, target, stream);                                            \
   }                                                                                                                         \
   extern "C" int se3mpc_simulator_step_##SUF(const se3mpc_simulator_params* sp, int B, double dt, const R* thrust, const R* torque, \
                                              const R* wind, long long wind_stride, double* time, R* pos, R* vel, R* att, R* omega, \
@@ -443,8 +410,8 @@ extern "C" int se3mpc_controller_reset(const se3mpc_controller_params* cp, int B
                                           const R* wind, long long wind_stride, int gust_step, const double* gust_wind,      \
                                           int stop_at_plan_end, R* log_state, R* log_cmd, double* log_time,                  \
                                           int32_t* steps_taken, void* stream) {                                             \
-    return closed_loop_impl<R>(cp, sp, B, nsteps, sim_dt, N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA, time, \
-                               pos, vel, att, omega, state, wind, wind_stride, gust_step, gust_wind, stop_at_plan_end,       \
+    return closed_loop_impl<R>(cp, sp, B, nsteps, sim_dt, PlanView<R>{N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA}, \
+                               time, pos, vel, att, omega, state, wind, wind_stride, gust_step, gust_wind, stop_at_plan_end, \
                                log_state, log_cmd, log_time, steps_taken, stream);                                          \
   }
 

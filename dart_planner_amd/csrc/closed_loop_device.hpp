@@ -1,6 +1,7 @@
 // closed_loop_device.hpp -- device code of the consumer side of the contract (plan sample -> geometric controller -> simulator step, one
-// drone per lane), shared by closed_loop.hip (its kernels and C entry points) and the fused receding-horizon loops of monte_carlo.hip and
-// mppi_closed_loop.hip (flight_step, fly_steps and the drone's LDS block).
+// drone per lane), shared by closed_loop.hip and smoother.hip (their kernels and C entry points: PlanView and its host rule, DroneRegs,
+// lane_loop) and the fused receding-horizon loops of monte_carlo.hip and mppi_closed_loop.hip (flight_step, fly_steps and the drone's LDS
+// block).
 // INCLUDE UNDER `#pragma clang fp contract(off)`: the controller's saturation / singularity / failsafe branches compare against values
 // NumPy computes without FMA (see closed_loop.hip).
 #pragma once
@@ -362,6 +363,36 @@ __device__ __forceinline__ void sample_plan(double t, int N, const double* __res
   }
 }
 
+// A plan operand of the C ABI as ONE kernel argument: N rows per drone, and for each of stamps [N], P, V, A [N][3] the base pointer and the
+// stride in elements from drone to drone (0: one plan shared by all; V, A null: zeros).  Members in the order of the C argument lists, so an
+// entry point builds it as PlanView<R>{N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA}.
+template <typename R>
+struct PlanView {
+  int N;
+  const double* ts; long long ts_stride;
+  const R* P; long long sP;
+  const R* V; long long sV;
+  const R* A; long long sA;
+  // drone b's plan as a view of its own; null stays null.  Pointers inside a struct carry no __restrict__: a kernel copies these four
+  // into __restrict__ locals.
+  __device__ __forceinline__ PlanView of(int b) const {
+    return {N, ts != nullptr ? ts + (size_t)b * ts_stride : nullptr, 0, P != nullptr ? P + (size_t)b * sP : nullptr, 0,
+            V != nullptr ? V + (size_t)b * sV : nullptr, 0, A != nullptr ? A + (size_t)b * sA : nullptr, 0};
+  }
+};
+
+// The host-side rule of a plan operand, in two parts because the entry points call them at different points (include/se3mpc.h; pinned by
+// tests/controller_checks.py check_plan_rules).  Shape: rows in [min_rows, 4096], strides >= 0 -- min_rows is 1 for se3mpc_control_plan_* and
+// se3mpc_closed_loop_* (sample_plan reads row N - 1), 0 for the smoother (no plan yet: zeros); every entry point checks it BEFORE its
+// B == 0 / nsteps == 0 no-op return.  Presence: stamps and positions there when there are rows -- the controller's entry points ask AFTER
+// the no-op return (an empty batch may come with NULL plans), the smoother's BEFORE it.
+template <typename R>
+static inline bool plan_shape_ok(const PlanView<R>& p, int min_rows) {
+  return p.N >= min_rows && p.N <= 4096 && p.ts_stride >= 0 && p.sP >= 0 && p.sV >= 0 && p.sA >= 0;
+}
+template <typename R>
+static inline bool plan_present(const PlanView<R>& p) { return p.N <= 0 || (p.ts != nullptr && p.P != nullptr); }
+
 // DroneSimulator.step (simulator.py:52-72)
 template <typename R>
 __device__ __forceinline__ void simulator_step(const SimDev<R>& m, R pos[3], R vel[3], R att[3], R omega[3], double& t, R thrust,
@@ -380,15 +411,23 @@ __device__ __forceinline__ void simulator_step(const SimDev<R>& m, R pos[3], R v
   t = t + dt_d;                                                                   // :67
 }
 
-// One flight step of one drone: the plan sampled at the drone's clock (a clock that does not advance searches from the start), the
-// geometric controller on the sample with yaw = yaw rate = 0, the simulator step under the command.  -> the command (th, tq).
-// The step of se3mpc_closed_loop_*, se3mpc_monte_carlo_* and se3mpc_mppi_closed_loop_*: one definition, hence the same bits.
+// The cursor before a step's sample: a clock that does not advance (sim_dt <= 0, or NaN) searches from the start.  Every loop that steps a
+// drone along a plan calls this, whichever sampler it uses.
+template <typename R>
+__device__ __forceinline__ void cursor_before_step(PlanCursor<R>& cur, double sim_dt) {
+  if (!(sim_dt > 0.0)) cur.idx = 0;
+}
+
+// One flight step of one drone: the plan sampled at the drone's clock, the geometric controller on the sample with yaw = yaw rate = 0, the
+// simulator step under the command.  -> the command (th, tq).
+// The step of se3mpc_closed_loop_* (through lane_loop), se3mpc_monte_carlo_* and se3mpc_mppi_closed_loop_* (through fly_steps): one
+// definition, hence the same bits.
 template <typename R>
 __device__ __forceinline__ void flight_step(const CtrlDev<R>& c, const SimDev<R>& m, CtrlRegs<R>& s, PlanCursor<R>& cur, int N,
                                             const double* ts, const R* P, const R* V, const R* A, R p[3], R v[3], R a[3], R w[3], double& t,
                                             R dt, double sim_dt, const R wd[3], R& th, R tq[3]) {
   R tp[3], tv[3], ta[3];
-  if (!(sim_dt > 0.0)) cur.idx = 0;
+  cursor_before_step(cur, sim_dt);
   sample_plan<R>(t, N, ts, P, V, A, tp, tv, ta, cur);
   int fl;
   control_step<R>(c, s, t, p, v, a, w, tp, tv, ta, (R)0, (R)0, th, tq, fl);
@@ -441,6 +480,40 @@ __device__ __forceinline__ void drone_store(const DroneBlock<R>& d, int b, R* __
   for (int i = 0; i < SE3MPC_CONTROLLER_STATE_WORDS; ++i) stateg[(size_t)b * SE3MPC_CONTROLLER_STATE_WORDS + i] = d.ctrl[i];
 }
 
+// One drone in registers: position, velocity, attitude, body rates, the wind on it and its clock.  Loaded from and stored to the global
+// [B][3] arrays and clocks (the one-drone-per-lane kernels; load_state alone where a kernel has no use for wind or clock) or a DroneBlock
+// (fly_steps).  The wind is an input: no store writes it.
+template <typename R>
+struct DroneRegs {
+  R p[3], v[3], a[3], w[3], wd[3];
+  double t;
+  __device__ __forceinline__ void load_state(int b, const R* __restrict__ pos, const R* __restrict__ vel, const R* __restrict__ att,
+                                             const R* __restrict__ omega) {
+    for (int i = 0; i < 3; ++i) { p[i] = pos[3 * b + i]; v[i] = vel[3 * b + i]; a[i] = att[3 * b + i]; w[i] = omega[3 * b + i]; }
+  }
+  // wind: null = none
+  __device__ __forceinline__ void load(int b, const R* __restrict__ pos, const R* __restrict__ vel, const R* __restrict__ att,
+                                       const R* __restrict__ omega, const R* __restrict__ wind, long long wind_stride,
+                                       const double* __restrict__ time) {
+    load_state(b, pos, vel, att, omega);
+    for (int i = 0; i < 3; ++i) wd[i] = wind != nullptr ? wind[(size_t)b * wind_stride + i] : (R)0;
+    t = time[b];
+  }
+  __device__ __forceinline__ void store(int b, R* __restrict__ pos, R* __restrict__ vel, R* __restrict__ att, R* __restrict__ omega,
+                                        double* __restrict__ time) const {
+    for (int i = 0; i < 3; ++i) { pos[3 * b + i] = p[i]; vel[3 * b + i] = v[i]; att[3 * b + i] = a[i]; omega[3 * b + i] = w[i]; }
+    time[b] = t;
+  }
+  __device__ __forceinline__ void load(const DroneBlock<R>& d) {
+    for (int i = 0; i < 3; ++i) { p[i] = d.vec[i]; v[i] = d.vec[3 + i]; a[i] = d.vec[6 + i]; w[i] = d.vec[9 + i]; wd[i] = d.vec[12 + i]; }
+    t = *d.time;
+  }
+  __device__ __forceinline__ void store(const DroneBlock<R>& d) const {
+    for (int i = 0; i < 3; ++i) { d.vec[i] = p[i]; d.vec[3 + i] = v[i]; d.vec[6 + i] = a[i]; d.vec[9 + i] = w[i]; }
+    *d.time = t;
+  }
+};
+
 // `n` flight steps of the drone in block d against its N-row plan, by ONE lane: state and controller record from LDS into registers,
 // the steps, and back.  after_step(step, pos) is called behind every step.  c and m by value: a copy of its own that the loop reads, not
 // the caller's kernel arguments (measured on se3mpc_mppi_closed_loop_f64: by reference the loop is 3 % slower).
@@ -448,20 +521,49 @@ template <typename R, typename F>
 __device__ __forceinline__ void fly_steps(const CtrlDev<R> c, const SimDev<R> m, const DroneBlock<R>& d, int N, int n, double sim_dt,
                                           F&& after_step) {
   CtrlRegs<R> s = load_ctrl<R>(d.ctrl);
-  R p[3], v[3], a[3], w[3], wd[3];
-  for (int i = 0; i < 3; ++i) { p[i] = d.vec[i]; v[i] = d.vec[3 + i]; a[i] = d.vec[6 + i]; w[i] = d.vec[9 + i]; wd[i] = d.vec[12 + i]; }
-  double t = *d.time;
+  DroneRegs<R> r;
+  r.load(d);
   const R dt = (R)sim_dt;
   PlanCursor<R> cur;
   cursor_reset(cur);
   for (int step = 0; step < n; ++step) {
     R th, tq[3];
-    flight_step<R>(c, m, s, cur, N, d.stamps, d.planP, d.planV, d.planA, p, v, a, w, t, dt, sim_dt, wd, th, tq);
-    after_step(step, p);
+    flight_step<R>(c, m, s, cur, N, d.stamps, d.planP, d.planV, d.planA, r.p, r.v, r.a, r.w, r.t, dt, sim_dt, r.wd, th, tq);
+    after_step(step, r.p);
   }
-  for (int i = 0; i < 3; ++i) { d.vec[i] = p[i]; d.vec[3 + i] = v[i]; d.vec[6 + i] = a[i]; d.vec[9 + i] = w[i]; }
-  *d.time = t;
+  r.store(d);
   store_ctrl<R>(d.ctrl, s);
+}
+
+// The loop of the one-drone-per-lane loop kernels (se3mpc_closed_loop_*, se3mpc_closed_loop_smoothed_*) for drone b of B: per step the
+// stop rule, row `step` of the state and clock logs, the gust, fly(step, th, tq) -- which produces the command and advances the drone --
+// and the command's log row.  -> the steps taken.  A drone that has stopped logs its standing state and NaN commands.
+// stop_at_plan_end: stop once the clock has passed ts_last (contract tests :130-131 / :263-264, `break`); logs: null = not kept.
+template <typename R, typename F>
+__device__ __forceinline__ int lane_loop(DroneRegs<R>& d, int b, int B, int nsteps, int gust_step, R gx, R gy, R gz, bool stop_at_plan_end,
+                                         double ts_last, R* __restrict__ log_state, R* __restrict__ log_cmd, double* __restrict__ log_time,
+                                         F&& fly) {
+  int taken = 0;
+  bool active = true;
+  for (int step = 0; step < nsteps; ++step) {
+    if (stop_at_plan_end && d.t > ts_last) active = false;
+    if (log_state != nullptr) {
+      R* ls = log_state + ((size_t)step * B + b) * 12;
+      for (int i = 0; i < 3; ++i) { ls[i] = d.p[i]; ls[3 + i] = d.v[i]; ls[6 + i] = d.a[i]; ls[9 + i] = d.w[i]; }
+    }
+    if (log_time != nullptr) log_time[(size_t)step * B + b] = d.t;
+    R th = (R)NAN, tq[3] = {(R)NAN, (R)NAN, (R)NAN};
+    if (active) {
+      if (step == gust_step) { d.wd[0] = gx; d.wd[1] = gy; d.wd[2] = gz; }      // the gust of contract test :293-296 (the controller does not see the wind)
+      fly(step, th, tq);
+      ++taken;
+    }
+    if (log_cmd != nullptr) {
+      R* lc = log_cmd + ((size_t)step * B + b) * 4;
+      lc[0] = th; lc[1] = tq[0]; lc[2] = tq[1]; lc[3] = tq[2];
+    }
+  }
+  return taken;
 }
 
 static inline int check_controller_params(const se3mpc_controller_params* p) {

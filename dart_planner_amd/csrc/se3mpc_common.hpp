@@ -94,6 +94,12 @@ inline int launch_status(const char* what) {
   return SE3MPC_OK;
 }
 
+// An argument error: `what` becomes se3mpc_last_error, the status passes through.
+inline int reject(int rc, const char* what) {
+  set_last_message(what);
+  return rc;
+}
+
 inline int grid_for(int B, int block) { return (B + block - 1) / block; }
 
 }  // namespace se3mpc

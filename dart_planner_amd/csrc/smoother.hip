@@ -5,7 +5,7 @@
 //   * update_trajectory       smoother.py:115-165   se3mpc_smoother_update_*
 //   * get_desired_state       smoother.py:167-213   se3mpc_smoother_desired_*  (and :64-113, :215-338, everything it calls)
 //   * the control-rate loop   get_desired_state -> GeometricController.compute_control -> DroneSimulator.step, `nsteps` times in ONE
-//                             launch: se3mpc_closed_loop_smoothed_* (control_step / simulator_step of closed_loop_device.hpp)
+//                             launch: se3mpc_closed_loop_smoothed_* (lane_loop / control_step / simulator_step of closed_loop_device.hpp)
 // The Butterworth filters the class builds (:56-62) are never applied by it and are not built here.
 //
 // Contraction is off in this file for the reason it is off in closed_loop.hip: the transition thresholds, the three per-call clamps, the
@@ -23,153 +23,119 @@ smoother_reset_kernel(int B, double* __restrict__ state) {
   for (int i = 0; i < SE3MPC_SMOOTHER_STATE_WORDS; ++i) s[i] = 0.0;               // smoother.py:28-46
 }
 
-// the plan of drone b of a (base, stride) operand; null stays null
-template <typename T>
-__device__ __forceinline__ const T* plan_of(const T* base, long long stride, int b) { return base != nullptr ? base + (size_t)b * stride : nullptr; }
-
 template <typename R>
 __global__ void __launch_bounds__(64)
-smoother_update_kernel(SmoothDev<R> d, int B, const double* __restrict__ now, int N_old, const double* __restrict__ ts_old, long long ts_old_stride,
-                       const R* __restrict__ P_old, long long sP_old, const R* __restrict__ V_old, long long sV_old, const R* __restrict__ A_old,
-                       long long sA_old, int N_new, const double* __restrict__ ts_new, long long ts_new_stride, const R* __restrict__ P_new,
-                       long long sP_new, const R* __restrict__ V_new, long long sV_new, const R* __restrict__ A_new, long long sA_new,
-                       double* __restrict__ state) {
+smoother_update_kernel(SmoothDev<R> d, int B, const double* __restrict__ now, PlanView<R> old_plan, PlanView<R> new_plan, double* __restrict__ state) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   SmoothRegs<R> s = load_smooth<R>(state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS);
-  smoother_update<R>(d, s, now[b], N_old, plan_of(ts_old, ts_old_stride, b), plan_of(P_old, sP_old, b), plan_of(V_old, sV_old, b),
-                     plan_of(A_old, sA_old, b), N_new, plan_of(ts_new, ts_new_stride, b), plan_of(P_new, sP_new, b), plan_of(V_new, sV_new, b),
-                     plan_of(A_new, sA_new, b), state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS + 9);
+  const PlanView<R> o = old_plan.of(b), n = new_plan.of(b);
+  smoother_update<R>(d, s, now[b], old_plan.N, o.ts, o.P, o.V, o.A, new_plan.N, n.ts, n.P, n.V, n.A, state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS + 9);
   store_smooth<R>(state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS, s);
 }
 
 template <typename R>
 __global__ void __launch_bounds__(64)
-smoother_desired_kernel(SmoothDev<R> d, int B, const double* __restrict__ now, const R* __restrict__ pos, const R* __restrict__ vel, int N,
-                        const double* __restrict__ timestamps, long long ts_stride, const R* __restrict__ P, long long strideP,
-                        const R* __restrict__ V, long long strideV, const R* __restrict__ A, long long strideA, double* __restrict__ state,
-                        R* __restrict__ target, int32_t* __restrict__ branch) {
+smoother_desired_kernel(SmoothDev<R> d, int B, const double* __restrict__ now, const R* __restrict__ pos, const R* __restrict__ vel, PlanView<R> plan,
+                        double* __restrict__ state, R* __restrict__ target, int32_t* __restrict__ branch) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   SmoothRegs<R> s = load_smooth<R>(state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS);
   const R p[3] = {pos[3 * b], pos[3 * b + 1], pos[3 * b + 2]}, v[3] = {vel[3 * b], vel[3 * b + 1], vel[3 * b + 2]};
+  const PlanView<R> rows = plan.of(b);
   R x[9];
   PlanCursor<R> cur;
   cursor_reset(cur);
-  const int br = smoother_desired<R>(d, s, state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS + 9, now[b], p, v, N, plan_of(timestamps, ts_stride, b), plan_of(P, strideP, b), plan_of(V, strideV, b),
-                                     plan_of(A, strideA, b), cur, x);
+  const int br = smoother_desired<R>(d, s, state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS + 9, now[b], p, v, plan.N, rows.ts, rows.P, rows.V, rows.A, cur, x);
   store_smooth<R>(state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS, s);
   if (target != nullptr) for (int i = 0; i < 9; ++i) target[9 * b + i] = x[i];
   if (branch != nullptr) branch[b] = br;
 }
 
-// ---- nsteps x (get_desired_state, compute_control, DroneSimulator.step) per drone in one launch; registers as closed_loop_kernel's
+// ---- nsteps x (get_desired_state, compute_control, DroneSimulator.step) per drone in one launch: lane_loop, as se3mpc_closed_loop_*, with
+// this step in place of flight_step and no stop rule
 template <typename R>
 __global__ void __launch_bounds__(64)
-closed_loop_smoothed_kernel(SmoothDev<R> d, CtrlDev<R> c, SimDev<R> m, int B, int nsteps, double sim_dt, int N, const double* __restrict__ timestamps,
-                            long long ts_stride, const R* __restrict__ P, long long strideP, const R* __restrict__ V, long long strideV,
-                            const R* __restrict__ A, long long strideA, double* __restrict__ time, R* __restrict__ pos, R* __restrict__ vel,
-                            R* __restrict__ att, R* __restrict__ omega, double* __restrict__ state, double* __restrict__ smoother_state,
-                            const R* __restrict__ wind, long long wind_stride, int gust_step, R gx, R gy, R gz, R* __restrict__ log_state,
-                            R* __restrict__ log_cmd, double* __restrict__ log_time, R* __restrict__ log_target) {
+closed_loop_smoothed_kernel(SmoothDev<R> d, CtrlDev<R> c, SimDev<R> m, int B, int nsteps, double sim_dt, PlanView<R> plan, double* __restrict__ time,
+                            R* __restrict__ pos, R* __restrict__ vel, R* __restrict__ att, R* __restrict__ omega, double* __restrict__ state,
+                            double* __restrict__ smoother_state, const R* __restrict__ wind, long long wind_stride, int gust_step, R gx, R gy, R gz,
+                            R* __restrict__ log_state, R* __restrict__ log_cmd, double* __restrict__ log_time, R* __restrict__ log_target) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   CtrlRegs<R> s = load_ctrl<R>(state + (size_t)b * SE3MPC_CONTROLLER_STATE_WORDS);
   SmoothRegs<R> sm = load_smooth<R>(smoother_state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS);
-  R p[3], v[3], a[3], w[3], wd[3] = {(R)0, (R)0, (R)0};
-  for (int i = 0; i < 3; ++i) {
-    p[i] = pos[3 * b + i]; v[i] = vel[3 * b + i]; a[i] = att[3 * b + i]; w[i] = omega[3 * b + i];
-    if (wind != nullptr) wd[i] = wind[(size_t)b * wind_stride + i];
-  }
-  double t = time[b];
-  const double* ts = plan_of(timestamps, ts_stride, b);
-  const R* Pb = plan_of(P, strideP, b);
-  const R* Vb = plan_of(V, strideV, b);
-  const R* Ab = plan_of(A, strideA, b);
+  DroneRegs<R> dr;
+  dr.load(b, pos, vel, att, omega, wind, wind_stride, time);
+  const int N = plan.N;
+  const PlanView<R> rows = plan.of(b);
+  const double* __restrict__ ts = rows.ts;
+  const R* __restrict__ Pb = rows.P;
+  const R* __restrict__ Vb = rows.V;
+  const R* __restrict__ Ab = rows.A;
   const R dt = (R)sim_dt;
   PlanCursor<R> cur;
   cursor_reset(cur);
-  for (int step = 0; step < nsteps; ++step) {
-    if (log_state != nullptr) {
-      R* ls = log_state + ((size_t)step * B + b) * 12;
-      for (int i = 0; i < 3; ++i) { ls[i] = p[i]; ls[3 + i] = v[i]; ls[6 + i] = a[i]; ls[9 + i] = w[i]; }
-    }
-    if (log_time != nullptr) log_time[(size_t)step * B + b] = t;
-    if (step == gust_step) { wd[0] = gx; wd[1] = gy; wd[2] = gz; }
-    R x[9], th, tq[3];
-    if (!(sim_dt > 0.0)) cur.idx = 0;                                             // a clock that does not advance searches from the start
-    smoother_desired<R>(d, sm, smoother_state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS + 9, t, p, v, N, ts, Pb, Vb, Ab, cur, x);   // main_improved.py:129
+  lane_loop<R>(dr, b, B, nsteps, gust_step, gx, gy, gz, false, 0.0, log_state, log_cmd, log_time, [&](int step, R& th, R* tq) {
+    R x[9];
+    cursor_before_step(cur, sim_dt);
+    smoother_desired<R>(d, sm, smoother_state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS + 9, dr.t, dr.p, dr.v, N, ts, Pb, Vb, Ab, cur, x);   // main_improved.py:129
     if (log_target != nullptr) {
       R* lt = log_target + ((size_t)step * B + b) * 9;
       for (int i = 0; i < 9; ++i) lt[i] = x[i];
     }
     int fl;
-    control_step<R>(c, s, t, p, v, a, w, x, x + 3, x + 6, (R)0, (R)0, th, tq, fl);   // main_improved.py:134-136
-    simulator_step<R>(m, p, v, a, w, t, th, tq, dt, sim_dt, wd);                  // main_improved.py:139
-    if (log_cmd != nullptr) {
-      R* lc = log_cmd + ((size_t)step * B + b) * 4;
-      lc[0] = th; lc[1] = tq[0]; lc[2] = tq[1]; lc[3] = tq[2];
-    }
-  }
-  for (int i = 0; i < 3; ++i) { pos[3 * b + i] = p[i]; vel[3 * b + i] = v[i]; att[3 * b + i] = a[i]; omega[3 * b + i] = w[i]; }
-  time[b] = t;
+    control_step<R>(c, s, dr.t, dr.p, dr.v, dr.a, dr.w, x, x + 3, x + 6, (R)0, (R)0, th, tq, fl);   // main_improved.py:134-136
+    simulator_step<R>(m, dr.p, dr.v, dr.a, dr.w, dr.t, th, tq, dt, sim_dt, dr.wd);                  // main_improved.py:139
+  });
+  dr.store(b, pos, vel, att, omega, time);
   store_ctrl<R>(state + (size_t)b * SE3MPC_CONTROLLER_STATE_WORDS, s);
   store_smooth<R>(smoother_state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS, sm);
 }
 
-static int reject(int rc, const char* what) {
-  set_last_message(what);
-  return rc;
-}
-
-// a plan operand of N rows: N in [0, 4096], strides >= 0, stamps and positions there when N > 0 (`required`)
-static int check_plan(int N, const void* ts, long long ts_stride, const void* P, long long sP, long long sV, long long sA, bool required,
-                      const char* what) {
-  if (N < 0 || N > 4096 || ts_stride < 0 || sP < 0 || sV < 0 || sA < 0) return reject(SE3MPC_ERR_SHAPE, what);
-  if (required && N > 0 && (ts == nullptr || P == nullptr)) return reject(SE3MPC_ERR_NULL, what);
+// a plan operand of the smoother's entry points (closed_loop_device.hpp: plan_shape_ok with no minimum, plan_present where `required`), both
+// parts before the caller's no-op return
+template <typename R>
+static int check_plan(const PlanView<R>& plan, bool required, const char* what) {
+  if (!plan_shape_ok(plan, 0)) return reject(SE3MPC_ERR_SHAPE, what);
+  if (required && !plan_present(plan)) return reject(SE3MPC_ERR_NULL, what);
   return SE3MPC_OK;
 }
 
 template <typename R>
-int smoother_update_impl(const se3mpc_smoother_params* mp, int B, const double* now, int N_old, const double* ts_old, long long ts_old_stride,
-                         const R* P_old, long long sP_old, const R* V_old, long long sV_old, const R* A_old, long long sA_old, int N_new,
-                         const double* ts_new, long long ts_new_stride, const R* P_new, long long sP_new, const R* V_new, long long sV_new,
-                         const R* A_new, long long sA_new, double* state, void* stream) {
+int smoother_update_impl(const se3mpc_smoother_params* mp, int B, const double* now, const PlanView<R>& old_plan, const PlanView<R>& new_plan,
+                         double* state, void* stream) {
   int rc = check_smoother_params(mp);
   if (rc) return reject(rc, "se3mpc_smoother_update: smoother parameters");
   if (B < 0) return reject(SE3MPC_ERR_SHAPE, "se3mpc_smoother_update: B < 0");
-  rc = check_plan(N_old, ts_old, ts_old_stride, P_old, sP_old, sV_old, sA_old, false, "se3mpc_smoother_update: old plan");
+  rc = check_plan(old_plan, false, "se3mpc_smoother_update: old plan");
   if (rc) return rc;
-  rc = check_plan(N_new, ts_new, ts_new_stride, P_new, sP_new, sV_new, sA_new, true, "se3mpc_smoother_update: new plan");
+  rc = check_plan(new_plan, true, "se3mpc_smoother_update: new plan");
   if (rc) return rc;
   if (B == 0) return SE3MPC_OK;
   if (!now || !state) return reject(SE3MPC_ERR_NULL, "se3mpc_smoother_update: now / state");
-  hipLaunchKernelGGL(smoother_update_kernel<R>, dim3(grid_for(B, 64)), dim3(64), 0, (hipStream_t)stream, make_smooth_dev<R>(*mp), B, now, N_old,
-                     ts_old, ts_old_stride, P_old, sP_old, V_old, sV_old, A_old, sA_old, N_new, ts_new, ts_new_stride, P_new, sP_new, V_new,
-                     sV_new, A_new, sA_new, state);
+  hipLaunchKernelGGL(smoother_update_kernel<R>, dim3(grid_for(B, 64)), dim3(64), 0, (hipStream_t)stream, make_smooth_dev<R>(*mp), B, now, old_plan,
+                     new_plan, state);
   return launch_status("se3mpc_smoother_update");
 }
 
 template <typename R>
-int smoother_desired_impl(const se3mpc_smoother_params* mp, int B, const double* now, const R* pos, const R* vel, int N, const double* timestamps,
-                          long long ts_stride, const R* P, long long strideP, const R* V, long long strideV, const R* A, long long strideA,
+int smoother_desired_impl(const se3mpc_smoother_params* mp, int B, const double* now, const R* pos, const R* vel, const PlanView<R>& plan,
                           double* state, R* target, int32_t* branch, void* stream) {
   int rc = check_smoother_params(mp);
   if (rc) return reject(rc, "se3mpc_smoother_desired: smoother parameters");
   if (B < 0) return reject(SE3MPC_ERR_SHAPE, "se3mpc_smoother_desired: B < 0");
-  rc = check_plan(N, timestamps, ts_stride, P, strideP, strideV, strideA, true, "se3mpc_smoother_desired: plan");
+  rc = check_plan(plan, true, "se3mpc_smoother_desired: plan");
   if (rc) return rc;
   if (B == 0) return SE3MPC_OK;
   if (!now || !pos || !vel || !state) return reject(SE3MPC_ERR_NULL, "se3mpc_smoother_desired: now / pos / vel / state");
   hipLaunchKernelGGL(smoother_desired_kernel<R>, dim3(grid_for(B, 64)), dim3(64), 0, (hipStream_t)stream, make_smooth_dev<R>(*mp), B, now, pos, vel,
-                     N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA, state, target, branch);
+                     plan, state, target, branch);
   return launch_status("se3mpc_smoother_desired");
 }
 
 template <typename R>
 int closed_loop_smoothed_impl(const se3mpc_smoother_params* mp, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B,
-                              int nsteps, double sim_dt, int N, const double* timestamps, long long ts_stride, const R* P, long long strideP,
-                              const R* V, long long strideV, const R* A, long long strideA, double* time, R* pos, R* vel, R* att, R* omega,
+                              int nsteps, double sim_dt, const PlanView<R>& plan, double* time, R* pos, R* vel, R* att, R* omega,
                               double* state, double* smoother_state, const R* wind, long long wind_stride, int gust_step,
                               const double* gust_wind, R* log_state, R* log_cmd, double* log_time, R* log_target, void* stream) {
   int rc = check_smoother_params(mp);
@@ -180,16 +146,15 @@ int closed_loop_smoothed_impl(const se3mpc_smoother_params* mp, const se3mpc_con
   if (rc) return reject(rc, "se3mpc_closed_loop_smoothed: simulator parameters");
   if (!std::isfinite(sim_dt)) return reject(SE3MPC_ERR_PARAM, "se3mpc_closed_loop_smoothed: sim_dt");
   if (B < 0 || nsteps < 0 || wind_stride < 0) return reject(SE3MPC_ERR_SHAPE, "se3mpc_closed_loop_smoothed: B / nsteps / wind_stride < 0");
-  rc = check_plan(N, timestamps, ts_stride, P, strideP, strideV, strideA, true, "se3mpc_closed_loop_smoothed: plan");
+  rc = check_plan(plan, true, "se3mpc_closed_loop_smoothed: plan");
   if (rc) return rc;
   if (B == 0 || nsteps == 0) return SE3MPC_OK;
   if (!time || !pos || !vel || !att || !omega || !state || !smoother_state || (gust_step >= 0 && !gust_wind))
     return reject(SE3MPC_ERR_NULL, "se3mpc_closed_loop_smoothed: a required operand is NULL");
   const R gx = gust_step >= 0 ? (R)gust_wind[0] : (R)0, gy = gust_step >= 0 ? (R)gust_wind[1] : (R)0, gz = gust_step >= 0 ? (R)gust_wind[2] : (R)0;
   hipLaunchKernelGGL(closed_loop_smoothed_kernel<R>, dim3(grid_for(B, 64)), dim3(64), 0, (hipStream_t)stream, make_smooth_dev<R>(*mp),
-                     make_ctrl_dev<R>(*cp), make_sim_dev<R>(*sp), B, nsteps, sim_dt, N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA,
-                     time, pos, vel, att, omega, state, smoother_state, wind, wind_stride, gust_step, gx, gy, gz, log_state, log_cmd, log_time,
-                     log_target);
+                     make_ctrl_dev<R>(*cp), make_sim_dev<R>(*sp), B, nsteps, sim_dt, plan, time, pos, vel, att, omega, state, smoother_state, wind,
+                     wind_stride, gust_step, gx, gy, gz, log_state, log_cmd, log_time, log_target);
   return launch_status("se3mpc_closed_loop_smoothed");
 }
 
@@ -220,15 +185,16 @@ extern "C" int se3mpc_smoother_reset(int B, double* state, void* stream) {
                                               const double* ts_new, long long ts_new_stride, const R* P_new, long long strideP_new,    \
                                               const R* V_new, long long strideV_new, const R* A_new, long long strideA_new,            \
                                               double* state, void* stream) {                                                          \
-    return smoother_update_impl<R>(mp, B, now, N_old, ts_old, ts_old_stride, P_old, strideP_old, V_old, strideV_old, A_old, strideA_old, \
-                                   N_new, ts_new, ts_new_stride, P_new, strideP_new, V_new, strideV_new, A_new, strideA_new, state, stream); \
+    return smoother_update_impl<R>(mp, B, now, PlanView<R>{N_old, ts_old, ts_old_stride, P_old, strideP_old, V_old, strideV_old, A_old, strideA_old}, \
+                                   PlanView<R>{N_new, ts_new, ts_new_stride, P_new, strideP_new, V_new, strideV_new, A_new, strideA_new}, state, \
+                                   stream);                                                                                         \
   }                                                                                                                                 \
   extern "C" int se3mpc_smoother_desired_##SUF(const se3mpc_smoother_params* mp, int B, const double* now, const R* pos, const R* vel, \
                                                int N, const double* timestamps, long long ts_stride, const R* P, long long strideP,    \
                                                const R* V, long long strideV, const R* A, long long strideA, double* state, R* target, \
                                                int32_t* branch, void* stream) {                                                       \
-    return smoother_desired_impl<R>(mp, B, now, pos, vel, N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA, state, target,  \
-                                    branch, stream);                                                                                \
+    return smoother_desired_impl<R>(mp, B, now, pos, vel, PlanView<R>{N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA}, state, \
+                                    target, branch, stream);                                                                        \
   }                                                                                                                                 \
   extern "C" int se3mpc_closed_loop_smoothed_##SUF(const se3mpc_smoother_params* mp, const se3mpc_controller_params* cp,               \
                                                    const se3mpc_simulator_params* sp, int B, int nsteps, double sim_dt, int N,         \
@@ -237,7 +203,7 @@ extern "C" int se3mpc_smoother_reset(int B, double* state, void* stream) {
                                                    R* vel, R* att, R* omega, double* state, double* smoother_state, const R* wind,     \
                                                    long long wind_stride, int gust_step, const double* gust_wind, R* log_state,        \
                                                    R* log_cmd, double* log_time, R* log_target, void* stream) {                        \
-    return closed_loop_smoothed_impl<R>(mp, cp, sp, B, nsteps, sim_dt, N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA,   \
+    return closed_loop_smoothed_impl<R>(mp, cp, sp, B, nsteps, sim_dt, PlanView<R>{N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA}, \
                                         time, pos, vel, att, omega, state, smoother_state, wind, wind_stride, gust_step, gust_wind,    \
                                         log_state, log_cmd, log_time, log_target, stream);                                          \
   }

@@ -543,19 +543,31 @@ class Ops:
         self.lib.controller_reset(cp, B, self.be.ptr(st), self.be.stream())
         return st
 
+    # The operands of the per-drone entry points.  Every front end below composes these, so a tensor of the wrong shape or dtype is a
+    # ValueError before any launch and never a pointer a kernel strides over.
     def _ctrl_state(self, state, B):
         """The controller records of B drones: float64 (B, 12)."""
         self.be.check(state, "state")
         if tuple(state.shape) != (B, CONTROLLER_STATE_WORDS) or self.be.suffix(state) != "f64":
-            raise ValueError("state: float64 (B, 12)")
+            raise ValueError(f"state: float64 ({B}, {CONTROLLER_STATE_WORDS})")
+
+    def _smoother_record(self, state, B):
+        self.be.check(state, "smoother state")
+        if tuple(state.shape) != (B, SMOOTHER_STATE_WORDS) or self.be.suffix(state) != "f64":
+            raise ValueError(f"smoother state: float64 ({B}, {SMOOTHER_STATE_WORDS})")
+
+    def _clock(self, now, B, name="now"):
+        self.be.check(now, name)
+        if tuple(now.shape) != (B,) or self.be.suffix(now) != "f64":
+            raise ValueError(f"{name}: float64 ({B},)")
 
     def _wind(self, wind, B, suf) -> int:
-        """A wind operand of the fused loops: None, one (3,) vector for all drones or (B, 3) rows, of the call's dtype -> its row stride."""
+        """A wind operand: None, one (3,) vector for all drones or (B, 3) rows, of the call's dtype -> its row stride."""
         if wind is None:
             return 0
         self.be.check(wind, "wind")
-        if self.be.suffix(wind) != suf or wind.shape[-1] != 3 or (wind.ndim == 2 and wind.shape[0] != B):
-            raise ValueError("wind: (3,) or (B, 3)")
+        if self.be.suffix(wind) != suf or tuple(wind.shape) not in ((3,), (B, 3)):
+            raise ValueError(f"wind: (3,) or ({B}, 3) {suf}, got {tuple(wind.shape)}")
         return 3 if wind.ndim == 2 else 0
 
     def _rows3(self, a, B, name, suf=None):
@@ -564,6 +576,69 @@ class Ops:
             raise ValueError(f"{name}: expected ({B}, 3) {suf or ''}, got {tuple(a.shape)}")
         return a
 
+    def _drone_state(self, B, suf, pos, vel, att, omega, **more):
+        """The four (B, 3) state arrays of B drones (and any further (B, 3) rows by name; None is skipped)."""
+        for nm, a in dict(pos=pos, vel=vel, att=att, omega=omega, **more).items():
+            if a is not None:
+                self._rows3(a, B, nm, suf)
+
+    def _per_drone(self, B, suf, **named):
+        """One value per drone: (B,) of the call's dtype; None is skipped."""
+        for nm, a in named.items():
+            if a is not None:
+                self.be.check(a, nm)
+                if tuple(a.shape) != (B,) or self.be.suffix(a) != suf:
+                    raise ValueError(f"{nm}: expected ({B},) {suf}, got {tuple(a.shape)}")
+
+    @staticmethod
+    def _gust(gust):
+        """gust = None or (step, (wx, wy, wz)) -> the (gust_step, gust_wind) arguments."""
+        if gust is None:
+            return -1, None
+        return int(gust[0]), (_C.c_double * 3)(*[float(x) for x in gust[1]])
+
+    def _loop_logs(self, nsteps, B, suf, log, target=False):
+        """The per-step logs of the loop kernels -> {} or dict(log_state (nsteps, B, 12), log_cmd (nsteps, B, 4), log_time (nsteps, B)[, log_target (nsteps, B, 9)])."""
+        if not log:
+            return {}
+        logs = dict(log_state=self.be.empty((nsteps, B, 12), suf), log_cmd=self.be.empty((nsteps, B, 4), suf), log_time=self.be.empty((nsteps, B), "f64"))
+        if target:
+            logs["log_target"] = self.be.empty((nsteps, B, 9), suf)
+        return logs
+
+    def _plan_ptrs(self, B, suf, timestamps, P, V, A, strides):
+        """A plan operand -> the nine plan arguments (N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA) of every entry point that takes one."""
+        self.be.check(timestamps, "timestamps")
+        if self.be.suffix(timestamps) != "f64":
+            raise ValueError("timestamps are float64")
+        N = timestamps.shape[-1]
+        ts_stride = N if timestamps.ndim == 2 else 0
+        if timestamps.ndim == 2 and timestamps.shape[0] != B:
+            raise ValueError("timestamps: (N,) or (B, N)")
+        if strides is None:
+            def st_of(a, nm):
+                if a is None:
+                    return 0
+                self.be.check(a, nm)
+                if self.be.suffix(a) != suf or a.ndim not in (2, 3) or a.shape[-2:] != (N, 3) or (a.ndim == 3 and a.shape[0] != B):
+                    raise ValueError(f"{nm}: expected ({N}, 3) or ({B}, {N}, 3) {suf}, got {tuple(a.shape)}")
+                return 3 * N if a.ndim == 3 else 0
+            sP, sV, sA = st_of(P, "P"), st_of(V, "V"), st_of(A, "A")
+        else:
+            sP, sV, sA = (int(x) for x in strides)
+            if hasattr(self.be, "elements_from"):              # explicit strides read past the views' own shapes: check the storage instead
+                for a, st, nm in ((P, sP, "P"), (V, sV, "V"), (A, sA, "A")):
+                    if a is not None and (st < 0 or (B - 1) * st + 3 * N > self.be.elements_from(a)):
+                        raise ValueError(f"{nm}: stride {st} x {B} plans of {N} rows runs past the tensor's storage")
+        return [N, self.be.ptr(timestamps), ts_stride, self.be.ptr(P), sP, self.be.ptr(V), sV, self.be.ptr(A), sA]
+
+    def _command_outputs(self, B, suf, want_body_rate):
+        """thrust (B,), torque (B, 3), flags int32 (B,)[, body_thrust (B,), body_rates (B, 3)] of a control call -> (dict, their five pointers)."""
+        out = dict(thrust=self.be.empty((B,), suf), torque=self.be.empty((B, 3), suf), flags=self.be.empty((B,), "i32"))
+        if want_body_rate:
+            out.update(body_thrust=self.be.empty((B,), suf), body_rates=self.be.empty((B, 3), suf))
+        return out, [self.be.ptr(out.get(k)) for k in ("thrust", "torque", "body_thrust", "body_rates", "flags")]
+
     def control(self, cp: ControllerParams, state, time, pos, vel, att, omega, dpos, dvel, dacc=None, yaw=None, yaw_rate=None,
                 want_body_rate: bool = False):
         """compute_control (+ compute_body_rate_command) for B drones.  time: float64 (B,); pos .. dvel, dacc: (B, 3);
@@ -571,24 +646,14 @@ class Ops:
         -> dict(thrust (B,), torque (B,3), flags int32 (B,)[, body_thrust (B,), body_rates (B,3)])."""
         B = time.shape[0]
         suf = self.be.suffix(pos)
-        for a, nm in ((pos, "pos"), (vel, "vel"), (att, "att"), (omega, "omega"), (dpos, "dpos"), (dvel, "dvel")):
-            self._rows3(a, B, nm, suf)
-        if dacc is not None:
-            self._rows3(dacc, B, "dacc", suf)
-        self.be.check(time, "time"); self.be.check(state, "state")
-        if self.be.suffix(time) != "f64" or tuple(state.shape) != (B, CONTROLLER_STATE_WORDS) or self.be.suffix(state) != "f64":
-            raise ValueError("time: float64 (B,); state: float64 (B, 12)")
-        thrust, torque = self.be.empty((B,), suf), self.be.empty((B, 3), suf)
-        flags = self.be.empty((B,), "i32")
-        bt = self.be.empty((B,), suf) if want_body_rate else None
-        br = self.be.empty((B, 3), suf) if want_body_rate else None
+        self._drone_state(B, suf, pos, vel, att, omega, dpos=dpos, dvel=dvel, dacc=dacc)
+        self._per_drone(B, suf, yaw=yaw, yaw_rate=yaw_rate)
+        self._clock(time, B, "time")
+        self._ctrl_state(state, B)
+        out, out_ptrs = self._command_outputs(B, suf, want_body_rate)
         self.lib.loop_call("control", suf, cp, B, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel), self.be.ptr(att),
                            self.be.ptr(omega), self.be.ptr(dpos), self.be.ptr(dvel), self.be.ptr(dacc), self.be.ptr(yaw),
-                           self.be.ptr(yaw_rate), self.be.ptr(state), self.be.ptr(thrust), self.be.ptr(torque), self.be.ptr(bt),
-                           self.be.ptr(br), self.be.ptr(flags), self.be.stream())
-        out = dict(thrust=thrust, torque=torque, flags=flags)
-        if want_body_rate:
-            out.update(body_thrust=bt, body_rates=br)
+                           self.be.ptr(yaw_rate), self.be.ptr(state), *out_ptrs, self.be.stream())
         return out
 
     def control_fast(self, cp: ControllerParams, state, dt: float, pos, vel, att, omega, dpos, dvel, dacc=None, yaw=None, yaw_rate=None,
@@ -598,23 +663,14 @@ class Ops:
         is the record se3mpc_control_* uses, updated in place.  -> dict(thrust (B,), torque (B,3), flags int32 (B,))."""
         B = pos.shape[0]
         suf = self.be.suffix(pos)
-        for a, nm in ((pos, "pos"), (vel, "vel"), (att, "att"), (omega, "omega"), (dpos, "dpos"), (dvel, "dvel")):
-            self._rows3(a, B, nm, suf)
-        if dacc is not None:
-            self._rows3(dacc, B, "dacc", suf)
-        for a, nm in ((yaw, "yaw"), (yaw_rate, "yaw_rate")):
-            if a is not None:
-                self.be.check(a, nm)
-                if tuple(a.shape) != (B,) or self.be.suffix(a) != suf:
-                    raise ValueError(f"{nm}: expected ({B},) {suf}")
+        self._drone_state(B, suf, pos, vel, att, omega, dpos=dpos, dvel=dvel, dacc=dacc)
+        self._per_drone(B, suf, yaw=yaw, yaw_rate=yaw_rate)
         self._ctrl_state(state, B)
-        thrust, torque = self.be.empty((B,), suf), self.be.empty((B, 3), suf)
-        flags = self.be.empty((B,), "i32")
+        out, (thrust, torque, _, _, flags) = self._command_outputs(B, suf, False)
         self.lib.loop_call("control_fast", suf, cp, float(vehicle_mass), float(vehicle_gravity), B, float(dt), self.be.ptr(pos), self.be.ptr(vel),
                            self.be.ptr(att), self.be.ptr(omega), self.be.ptr(dpos), self.be.ptr(dvel), self.be.ptr(dacc), self.be.ptr(yaw),
-                           self.be.ptr(yaw_rate), self.be.ptr(state), self.be.ptr(thrust), self.be.ptr(torque), self.be.ptr(flags),
-                           self.be.stream())
-        return dict(thrust=thrust, torque=torque, flags=flags)
+                           self.be.ptr(yaw_rate), self.be.ptr(state), thrust, torque, flags, self.be.stream())
+        return out
 
     def monte_carlo(self, params: Params, cp: ControllerParams, sp: SimulatorParams, state, time, pos, vel, att, omega, goal, cycles: int,
                     substeps: int, sim_dt: float, wind=None, want_last_plan: bool = False):
@@ -624,11 +680,9 @@ class Ops:
         x, accelerations, info of the last cycle's plan if asked for)."""
         B = pos.shape[0]
         suf = self.be.suffix(pos)
-        for a, nm in ((pos, "pos"), (vel, "vel"), (att, "att"), (omega, "omega"), (goal, "goal")):
-            self._rows3(a, B, nm, suf)
-        self.be.check(state, "state"); self.be.check(time, "time")
-        if tuple(state.shape) != (B, CONTROLLER_STATE_WORDS) or self.be.suffix(state) != "f64" or tuple(time.shape) != (B,) or self.be.suffix(time) != "f64":
-            raise ValueError("state: float64 (B, 12); time: float64 (B,)")
+        self._drone_state(B, suf, pos, vel, att, omega, goal=goal)
+        self._ctrl_state(state, B)
+        self._clock(time, B, "time")
         w_stride = self._wind(wind, B, suf)
         N = params.horizon
         over = self.be.empty((1,), "i32")
@@ -655,22 +709,18 @@ class Ops:
         B = pos.shape[0]
         suf = self.be.suffix(pos)
         N = params.horizon
-        for a, nm in ((pos, "pos"), (vel, "vel"), (att, "att"), (omega, "omega"), (goal, "goal")):
-            self._rows3(a, B, nm, suf)
-        self.be.check(state, "state"); self.be.check(time, "time"); self.be.check(U, "U")
-        if tuple(state.shape) != (B, CONTROLLER_STATE_WORDS) or self.be.suffix(state) != "f64" or tuple(time.shape) != (B,) or self.be.suffix(time) != "f64":
-            raise ValueError("state: float64 (B, 12); time: float64 (B,)")
+        self._drone_state(B, suf, pos, vel, att, omega, goal=goal)
+        self._ctrl_state(state, B)
+        self._clock(time, B, "time")
+        self.be.check(U, "U")
         if tuple(U.shape) != (B, N, 3) or self.be.suffix(U) != suf:
             raise ValueError(f"U: expected ({B}, {N}, 3) {suf}, got {tuple(U.shape)}")
         w_stride = self._wind(wind, B, suf)
         K = 0
         if spheres is not None:
             K = self._spheres(spheres, suf)
-        if clearance is not None:
-            self.be.check(clearance, "clearance")
-            if tuple(clearance.shape) != (B,) or self.be.suffix(clearance) != suf:
-                raise ValueError(f"clearance: expected ({B},) {suf}")
-        elif want_clearance and K:
+        self._per_drone(B, suf, clearance=clearance)
+        if clearance is None and want_clearance and K:
             clearance = self.be.empty((B,), suf)
             clearance[...] = float("inf")
         cost = self.be.empty((B,), suf)
@@ -708,6 +758,7 @@ class Ops:
         suf = self.be.suffix(att)
         for a, nm in ((att, "att"), (omega, "omega"), (b3_des, "b3_des")):
             self._rows3(a, B, nm, suf)
+        self._per_drone(B, suf, yaw=yaw, yaw_rate=yaw_rate)
         self._ctrl_state(state, B)
         mat = None
         if inertia is not None:
@@ -726,35 +777,11 @@ class Ops:
         B = yaw_vector.shape[0]
         suf = self.be.suffix(yaw_vector)
         self._rows3(yaw_vector, B, "yaw_vector", suf); self._rows3(b3_des, B, "b3_des", suf)
+        self._per_drone(B, suf, current_yaw=current_yaw)
         frame, ca, sg = self.be.empty((B, 9), suf), self.be.empty((B,), suf), self.be.empty((B,), "i32")
         self.lib.loop_call("controller_desired_frame", suf, cp, B, int(method), self.be.ptr(yaw_vector), self.be.ptr(b3_des), self.be.ptr(current_yaw),
                            self.be.ptr(frame), self.be.ptr(ca), self.be.ptr(sg), self.be.stream())
         return dict(frame=frame, cos_angle=ca, singular=sg)
-
-    def _plan_args(self, B, suf, timestamps, P, V, A, strides):
-        self.be.check(timestamps, "timestamps")
-        if self.be.suffix(timestamps) != "f64":
-            raise ValueError("timestamps are float64")
-        N = timestamps.shape[-1]
-        ts_stride = N if timestamps.ndim == 2 else 0
-        if timestamps.ndim == 2 and timestamps.shape[0] != B:
-            raise ValueError("timestamps: (N,) or (B, N)")
-        if strides is None:
-            def st_of(a, nm):
-                if a is None:
-                    return 0
-                self.be.check(a, nm)
-                if self.be.suffix(a) != suf or a.ndim not in (2, 3) or a.shape[-2:] != (N, 3) or (a.ndim == 3 and a.shape[0] != B):
-                    raise ValueError(f"{nm}: expected ({N}, 3) or ({B}, {N}, 3) {suf}, got {tuple(a.shape)}")
-                return 3 * N if a.ndim == 3 else 0
-            sP, sV, sA = st_of(P, "P"), st_of(V, "V"), st_of(A, "A")
-        else:
-            sP, sV, sA = (int(x) for x in strides)
-            if hasattr(self.be, "elements_from"):              # explicit strides read past the views' own shapes: check the storage instead
-                for a, st, nm in ((P, sP, "P"), (V, sV, "V"), (A, sA, "A")):
-                    if a is not None and (st < 0 or (B - 1) * st + 3 * N > self.be.elements_from(a)):
-                        raise ValueError(f"{nm}: stride {st} x {B} plans of {N} rows runs past the tensor's storage")
-        return N, ts_stride, sP, sV, sA
 
     def control_plan(self, cp: ControllerParams, state, time, sample_time, pos, vel, att, omega, timestamps, P, V=None, A=None,
                      strides=None, want_body_rate: bool = False, want_target: bool = False):
@@ -762,36 +789,26 @@ class Ops:
         sample_time (float64 (B,)).  Plans as in :meth:`closed_loop`.  -> dict like :meth:`control` (+ target (B, 9))."""
         B = time.shape[0]
         suf = self.be.suffix(pos)
-        for a, nm in ((pos, "pos"), (vel, "vel"), (att, "att"), (omega, "omega")):
-            self._rows3(a, B, nm, suf)
-        N, ts_stride, sP, sV, sA = self._plan_args(B, suf, timestamps, P, V, A, strides)
-        thrust, torque = self.be.empty((B,), suf), self.be.empty((B, 3), suf)
-        flags = self.be.empty((B,), "i32")
-        bt = self.be.empty((B,), suf) if want_body_rate else None
-        br = self.be.empty((B, 3), suf) if want_body_rate else None
-        tg = self.be.empty((B, 9), suf) if want_target else None
-        self.lib.loop_call("control_plan", suf, cp, B, self.be.ptr(time), self.be.ptr(sample_time), self.be.ptr(pos), self.be.ptr(vel),
-                           self.be.ptr(att), self.be.ptr(omega), N, self.be.ptr(timestamps), ts_stride, self.be.ptr(P), sP, self.be.ptr(V), sV,
-                           self.be.ptr(A), sA, self.be.ptr(state), self.be.ptr(thrust), self.be.ptr(torque), self.be.ptr(bt), self.be.ptr(br),
-                           self.be.ptr(flags), self.be.ptr(tg), self.be.stream())
-        out = dict(thrust=thrust, torque=torque, flags=flags)
-        if want_body_rate:
-            out.update(body_thrust=bt, body_rates=br)
+        self._drone_state(B, suf, pos, vel, att, omega)
+        self._clock(time, B, "time"); self._clock(sample_time, B, "sample_time")
+        self._ctrl_state(state, B)
+        plan = self._plan_ptrs(B, suf, timestamps, P, V, A, strides)
+        out, out_ptrs = self._command_outputs(B, suf, want_body_rate)
         if want_target:
-            out["target"] = tg
+            out["target"] = self.be.empty((B, 9), suf)
+        self.lib.loop_call("control_plan", suf, cp, B, self.be.ptr(time), self.be.ptr(sample_time), self.be.ptr(pos), self.be.ptr(vel),
+                           self.be.ptr(att), self.be.ptr(omega), *plan, self.be.ptr(state), *out_ptrs, self.be.ptr(out.get("target")), self.be.stream())
         return out
 
     def simulator_step(self, sp: SimulatorParams, time, pos, vel, att, omega, thrust, torque, dt: float, wind=None):
-        """DroneSimulator.step for B drones: advances time, pos, vel, att, omega in place."""
+        """DroneSimulator.step for B drones: advances time, pos, vel, att, omega in place.  thrust (B,), torque (B, 3); wind as in
+        :meth:`closed_loop`."""
         B = time.shape[0]
         suf = self.be.suffix(pos)
-        for a, nm in ((pos, "pos"), (vel, "vel"), (att, "att"), (omega, "omega"), (torque, "torque")):
-            self._rows3(a, B, nm, suf)
-        self.be.check(thrust, "thrust")
-        w_stride = 0
-        if wind is not None:
-            self.be.check(wind, "wind")
-            w_stride = 3 if wind.ndim == 2 else 0
+        self._drone_state(B, suf, pos, vel, att, omega, torque=torque)
+        self._clock(time, B, "time")
+        self._per_drone(B, suf, thrust=thrust)
+        w_stride = self._wind(wind, B, suf)
         self.lib.loop_call("simulator_step", suf, sp, B, float(dt), self.be.ptr(thrust), self.be.ptr(torque), self.be.ptr(wind), w_stride,
                            self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega), self.be.stream())
 
@@ -805,32 +822,19 @@ class Ops:
         -> dict(steps_taken int32 (B,)[, log_state (nsteps, B, 12), log_cmd (nsteps, B, 4), log_time (nsteps, B)])."""
         B = time.shape[0]
         suf = self.be.suffix(pos)
-        for a, nm in ((pos, "pos"), (vel, "vel"), (att, "att"), (omega, "omega")):
-            self._rows3(a, B, nm, suf)
-        N, ts_stride, sP, sV, sA = self._plan_args(B, suf, timestamps, P, V, A, strides)
-        w_stride = 0
-        if wind is not None:
-            self.be.check(wind, "wind")
-            if self.be.suffix(wind) != suf or wind.shape[-1] != 3:
-                raise ValueError("wind: (3,) or (B, 3)")
-            w_stride = 3 if wind.ndim == 2 else 0
-        gust_step, gust_vec = -1, None
-        if gust is not None:
-            gust_step = int(gust[0])
-            gust_vec = (_C.c_double * 3)(*[float(x) for x in gust[1]])
-        ls = self.be.empty((nsteps, B, 12), suf) if log else None
-        lc = self.be.empty((nsteps, B, 4), suf) if log else None
-        lt = self.be.empty((nsteps, B), "f64") if log else None
+        self._drone_state(B, suf, pos, vel, att, omega)
+        self._clock(time, B, "time")
+        self._ctrl_state(state, B)
+        plan = self._plan_ptrs(B, suf, timestamps, P, V, A, strides)
+        w_stride = self._wind(wind, B, suf)
+        gust_step, gust_vec = self._gust(gust)
+        logs = self._loop_logs(nsteps, B, suf, log)
         taken = self.be.empty((B,), "i32")
-        self.lib.loop_call("closed_loop", suf, cp, sp, B, int(nsteps), float(sim_dt), N, self.be.ptr(timestamps), ts_stride,
-                           self.be.ptr(P), sP, self.be.ptr(V), sV, self.be.ptr(A), sA, self.be.ptr(time), self.be.ptr(pos),
+        self.lib.loop_call("closed_loop", suf, cp, sp, B, int(nsteps), float(sim_dt), *plan, self.be.ptr(time), self.be.ptr(pos),
                            self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega), self.be.ptr(state), self.be.ptr(wind), w_stride,
-                           gust_step, gust_vec, int(bool(stop_at_plan_end)), self.be.ptr(ls), self.be.ptr(lc), self.be.ptr(lt),
-                           self.be.ptr(taken), self.be.stream())
-        out = dict(steps_taken=taken)
-        if log:
-            out.update(log_state=ls, log_cmd=lc, log_time=lt)
-        return out
+                           gust_step, gust_vec, int(bool(stop_at_plan_end)), self.be.ptr(logs.get("log_state")), self.be.ptr(logs.get("log_cmd")),
+                           self.be.ptr(logs.get("log_time")), self.be.ptr(taken), self.be.stream())
+        return dict(steps_taken=taken, **logs)
 
     # ------------------------------------------------------------------ TrajectorySmoother (per-drone rows)
     def smoother_state(self, B: int):
@@ -838,21 +842,6 @@ class Ops:
         st = self.be.empty((B, SMOOTHER_STATE_WORDS), "f64")
         self.lib.smoother_reset(B, self.be.ptr(st), self.be.stream())
         return st
-
-    def _smoother_record(self, state, B):
-        self.be.check(state, "smoother state")
-        if tuple(state.shape) != (B, SMOOTHER_STATE_WORDS) or self.be.suffix(state) != "f64":
-            raise ValueError(f"smoother state: float64 ({B}, {SMOOTHER_STATE_WORDS})")
-
-    def _clock(self, now, B, name="now"):
-        self.be.check(now, name)
-        if tuple(now.shape) != (B,) or self.be.suffix(now) != "f64":
-            raise ValueError(f"{name}: float64 ({B},)")
-
-    def _plan_ptrs(self, B, suf, timestamps, P, V, A, strides):
-        """The nine plan arguments (N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA) of the smoother's entry points."""
-        N, ts_stride, sP, sV, sA = self._plan_args(B, suf, timestamps, P, V, A, strides)
-        return [N, self.be.ptr(timestamps), ts_stride, self.be.ptr(P), sP, self.be.ptr(V), sV, self.be.ptr(A), sA]
 
     def smoother_update(self, mp: SmootherParams, state, now, timestamps, P, V=None, A=None, strides=None, old=None, old_strides=None) -> None:
         """update_trajectory for B drones at the clocks now float64 (B,): the new plan (timestamps, P, V, A[, strides]) as in :meth:`closed_loop`
@@ -891,27 +880,20 @@ class Ops:
         (nsteps, B, 9)])."""
         B = time.shape[0]
         suf = self.be.suffix(pos)
-        for a, nm in ((pos, "pos"), (vel, "vel"), (att, "att"), (omega, "omega")):
-            self._rows3(a, B, nm, suf)
+        self._drone_state(B, suf, pos, vel, att, omega)
         self._clock(time, B, "time")
         self._ctrl_state(state, B)
         self._smoother_record(smoother_state, B)
         plan = self._plan_ptrs(B, suf, timestamps, P, V, A, strides)
         w_stride = self._wind(wind, B, suf)
-        gust_step, gust_vec = -1, None
-        if gust is not None:
-            gust_step = int(gust[0])
-            gust_vec = (_C.c_double * 3)(*[float(x) for x in gust[1]])
+        gust_step, gust_vec = self._gust(gust)
         nsteps = int(nsteps)
-        ls = self.be.empty((nsteps, B, 12), suf) if log else None
-        lc = self.be.empty((nsteps, B, 4), suf) if log else None
-        lt = self.be.empty((nsteps, B), "f64") if log else None
-        lg = self.be.empty((nsteps, B, 9), suf) if log else None
+        logs = self._loop_logs(nsteps, B, suf, log, target=True)
         self.lib.loop_call("closed_loop_smoothed", suf, mp, cp, sp, B, nsteps, float(sim_dt), *plan, self.be.ptr(time), self.be.ptr(pos),
                            self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega), self.be.ptr(state), self.be.ptr(smoother_state),
-                           self.be.ptr(wind), w_stride, gust_step, gust_vec, self.be.ptr(ls), self.be.ptr(lc), self.be.ptr(lt), self.be.ptr(lg),
-                           self.be.stream())
-        return dict(log_state=ls, log_cmd=lc, log_time=lt, log_target=lg) if log else {}
+                           self.be.ptr(wind), w_stride, gust_step, gust_vec, self.be.ptr(logs.get("log_state")), self.be.ptr(logs.get("log_cmd")),
+                           self.be.ptr(logs.get("log_time")), self.be.ptr(logs.get("log_target")), self.be.stream())
+        return logs
 
     # ------------------------------------------------------------------ problem layout
     def solve(self, params: Params, p0, v0, goal, x0=None, want_trajectory=True, out=None):

@@ -362,3 +362,268 @@ def check_closed_loop_vs_oracle(h, B=96, N=12, nsteps=40, seed=0, per_drone_plan
         err = np.max(np.abs(ls - ref), axis=(0, 2))
         assert np.median(err) <= 5e-3 and np.mean(err <= 5e-2) >= 0.9, (np.median(err), np.mean(err <= 5e-2))
     return float(np.max(np.abs(ls - ref)))
+
+
+def check_plan_rules(h):
+    """The status every entry point with a plan operand returns for every plan argument, in the harness's precision: se3mpc_control_plan_*,
+    se3mpc_closed_loop_*, se3mpc_smoother_update_* (old and new plan), se3mpc_smoother_desired_*, se3mpc_closed_loop_smoothed_*.
+
+    Where the expectations come from.  include/se3mpc.h: a negative row count or stride and more than 4096 rows are SE3MPC_ERR_SHAPE, a NULL
+    required operand is SE3MPC_ERR_NULL, V and A may be NULL, B = 0 / nsteps = 0 is a no-op that returns SE3MPC_OK, and the smoother's entry
+    points accept a plan of 0 rows.  The header is silent on the rest, and there the behaviour of the library decides (characterised once,
+    and pinned here): (a) the controller's two entry points need at least one row, the smoother's take none; (b) the shape of a plan is
+    checked before the no-op return in both families, but its stamps and positions are looked at AFTER that return by the controller's entry
+    points (an empty batch may come with NULL plans) and BEFORE it by the smoother's; (c) the OLD plan of se3mpc_smoother_update_* is never
+    required (a drone without a trajectory does not read it); (d) parameter errors win over plan errors, shape errors over NULL errors.
+    B = 2 drones, plans of 2 rows (one 4096-row plan for the upper end of the range); a rejected or no-op call leaves every in/out and
+    output buffer, pre-filled with a byte pattern, untouched."""
+    from dart_planner_amd.capi import SmootherParams
+    ops, lib = h.ops, h.ops.lib
+    ptr = ops.be.ptr
+    suf = "f64" if h.dt == np.float64 else "f32"
+    OK, NULL, SHAPE, PARAM = 0, -1, -3, -4
+    B, ROWS = 2, 4096
+    cp, sp, mp = lib.controller_default_params(), lib.simulator_default_params(), SmootherParams.reference_defaults()
+    real = lambda a: h.to_dev(np.ascontiguousarray(np.asarray(a).astype(h.dt)))
+    ts = h.to_dev(np.arange(ROWS) * 0.01)
+    P, V, A = real(np.zeros((ROWS, 3))), real(np.zeros((ROWS, 3))), real(np.zeros((ROWS, 3)))
+    ctrl0, smooth0 = np.array(h.to_host(ops.controller_state(cp, B))), np.array(h.to_host(ops.smoother_state(B)))
+    pattern = lambda shape, ty: h.to_dev(np.frombuffer(bytearray(b"\x5a" * (int(np.prod(shape)) * np.dtype(ty).itemsize)), dtype=ty).reshape(shape))
+
+    def plan(N=2, stamps=True, pos=True, vel=True, acc=True, strides=(0, 0, 0, 0)):
+        return [N, ptr(ts) if stamps else 0, strides[0], ptr(P) if pos else 0, strides[1], ptr(V) if vel else 0, strides[2], ptr(A) if acc else 0, strides[3]]
+
+    def buffers():
+        b = dict(time=h.to_dev(np.zeros(B)), sample=h.to_dev(np.zeros(B)), state=h.to_dev(ctrl0.copy()), sm=h.to_dev(smooth0.copy()))
+        for k in ("pos", "vel", "att", "om"):
+            b[k] = real(np.zeros((B, 3)))
+        b.update(thrust=pattern((B,), h.dt), torque=pattern((B, 3), h.dt), flags=pattern((B,), np.int32), target=pattern((B, 9), h.dt),
+                 branch=pattern((B,), np.int32), taken=pattern((B,), np.int32), log_state=pattern((3, B, 12), h.dt), log_cmd=pattern((3, B, 4), h.dt),
+                 log_time=pattern((3, B), np.float64), log_target=pattern((3, B, 9), h.dt))
+        return b
+
+    def control_plan(b, pl, B_=B, nsteps=None, **kw):
+        return lib.loop_status("control_plan", suf, kw.get("cp", cp), B_, ptr(b["time"]), ptr(b["sample"]), ptr(b["pos"]), ptr(b["vel"]), ptr(b["att"]),
+                               ptr(b["om"]), *pl, 0 if kw.get("no_state") else ptr(b["state"]), ptr(b["thrust"]), ptr(b["torque"]), 0, 0, ptr(b["flags"]),
+                               ptr(b["target"]), 0)
+
+    def closed_loop(b, pl, B_=B, nsteps=3, **kw):
+        return lib.loop_status("closed_loop", suf, cp, sp, B_, nsteps, kw.get("sim_dt", 0.01), *pl, ptr(b["time"]), ptr(b["pos"]), ptr(b["vel"]), ptr(b["att"]),
+                               ptr(b["om"]), 0 if kw.get("no_state") else ptr(b["state"]), 0, kw.get("wind_stride", 0), -1, None, 0, ptr(b["log_state"]),
+                               ptr(b["log_cmd"]), ptr(b["log_time"]), ptr(b["taken"]), 0)
+
+    def update_new(b, pl, B_=B, nsteps=None, old=None, **kw):
+        return lib.loop_status("smoother_update", suf, mp, B_, ptr(b["time"]), *(plan() if old is None else old), *pl, 0 if kw.get("no_state") else ptr(b["sm"]), 0)
+
+    def update_old(b, pl, B_=B, nsteps=None, **kw):
+        return update_new(b, plan(), B_, old=pl, **kw)
+
+    def desired(b, pl, B_=B, nsteps=None, **kw):
+        return lib.loop_status("smoother_desired", suf, mp, B_, ptr(b["time"]), ptr(b["pos"]), ptr(b["vel"]), *pl, 0 if kw.get("no_state") else ptr(b["sm"]),
+                               ptr(b["target"]), ptr(b["branch"]), 0)
+
+    def smoothed(b, pl, B_=B, nsteps=3, **kw):
+        return lib.loop_status("closed_loop_smoothed", suf, mp, cp, sp, B_, nsteps, kw.get("sim_dt", 0.01), *pl, ptr(b["time"]), ptr(b["pos"]), ptr(b["vel"]),
+                               ptr(b["att"]), ptr(b["om"]), 0 if kw.get("no_state") else ptr(b["state"]), ptr(b["sm"]), 0, kw.get("wind_stride", 0), -1, None,
+                               ptr(b["log_state"]), ptr(b["log_cmd"]), ptr(b["log_time"]), ptr(b["log_target"]), 0)
+
+    def call(fn, pl, **kw):
+        """-> the status; a call that is rejected or has nothing to do must not have written a byte"""
+        b = buffers()
+        before = {k: np.array(h.to_host(v)).tobytes() for k, v in b.items()}
+        rc = fn(b, pl, **kw)
+        if rc != OK or kw.get("B_", B) == 0 or kw.get("nsteps", 1) == 0:
+            for k, v in b.items():
+                assert np.array(h.to_host(v)).tobytes() == before[k], (fn.__name__, pl, kw, k)
+        return rc
+
+    def expected(min_rows, presence, empty, N=2, stamps=True, pos=True, vel=True, acc=True, strides=(0, 0, 0, 0)):
+        """min_rows: 1 controller family, 0 smoother family; presence: "after" (the no-op return), "before" it, or None (never required)"""
+        if N < min_rows or N > 4096 or min(strides) < 0:
+            return SHAPE
+        missing = N > 0 and not (stamps and pos)
+        if presence == "before" and missing:
+            return NULL
+        if empty:
+            return OK
+        return NULL if presence == "after" and missing else OK
+
+    cases = [dict(N=n) for n in (-1, 0, 1, 4096, 4097)]
+    cases += [dict(strides=tuple(-1 if i == j else 0 for i in range(4))) for j in range(4)]
+    cases += [dict(stamps=False), dict(pos=False), dict(vel=False), dict(acc=False), dict(vel=False, acc=False)]
+    cases += [dict(N=0, stamps=False, pos=False), dict(N=-1, stamps=False), dict(N=4097, pos=False), dict(stamps=False, strides=(0, 0, -1, 0))]   # two errors at once
+    entries = [(control_plan, 1, "after", False), (closed_loop, 1, "after", True), (update_old, 0, None, False), (update_new, 0, "before", False),
+               (desired, 0, "before", False), (smoothed, 0, "before", True)]
+    checked = 0
+    for fn, min_rows, presence, has_nsteps in entries:
+        for case in cases:
+            for kw in [dict(), dict(B_=0)] + ([dict(nsteps=0)] if has_nsteps else []):
+                want = expected(min_rows, presence, bool(kw), **case)
+                got = call(fn, plan(**case), **kw)
+                assert got == want, (fn.__name__, suf, case, kw, got, want)
+                checked += 1
+    assert checked == 18 * (4 * 2 + 2 * 3)
+    # the two traps, literally
+    assert call(closed_loop, plan(stamps=False, pos=False), B_=0) == OK and call(control_plan, plan(stamps=False, pos=False), B_=0) == OK
+    assert call(closed_loop, plan(N=0)) == SHAPE and call(control_plan, plan(N=0)) == SHAPE
+    assert call(smoothed, plan(stamps=False), B_=0) == NULL and call(smoothed, plan(pos=False), nsteps=0) == NULL and call(desired, plan(pos=False), B_=0) == NULL
+    assert "plan" in lib.last_error()
+    assert call(update_new, plan(stamps=False), B_=0) == NULL and call(update_old, plan(stamps=False, pos=False)) == OK
+    assert call(smoothed, plan(N=0)) == OK and call(desired, plan(N=0, stamps=False, pos=False)) == OK and call(update_new, plan(N=0)) == OK
+    # which of two errors wins
+    for fn in (closed_loop, smoothed):
+        assert call(fn, plan(N=-1), sim_dt=float("nan")) == PARAM                   # parameters before the plan
+        assert call(fn, plan(stamps=False), wind_stride=-1) == SHAPE               # any shape error before any NULL
+        assert call(fn, plan(N=4097), B_=-1) == SHAPE and call(fn, plan(stamps=False), B_=-1) == SHAPE
+    for fn in (control_plan, closed_loop, update_new, desired, smoothed):
+        assert call(fn, plan(N=-1), no_state=True) == SHAPE and call(fn, plan(pos=False), no_state=True) == NULL
+    assert call(update_new, plan(pos=False), old=plan(N=-1)) == SHAPE and call(update_new, plan(N=4097), old=plan(stamps=False)) == SHAPE
+    bad = lib.controller_default_params(); bad.mass = 0.0
+    assert call(control_plan, plan(N=0), cp=bad) == PARAM
+
+
+def record_launch_sequences(ops, monkeypatch):
+    """The library calls of every public method of ClosedLoopMonteCarlo at B = 2, N = 6, 3 cycles x 2 substeps, 8 samples x 1 iteration, as
+    {method: [one line per call]}: the entry point, then its arguments -- scalars as they are, a parameter struct by its class name, a
+    non-NULL address as P (NULL stays 0).  Host logic only: the calls are recorded, not made (8 samples is below what se3mpc_mppi_* runs), on
+    zero-filled buffers (so the overflow counter run_fused reads is 0).  Also asserted here, on the recorded addresses: run() hands every
+    cycle the same plan tensors, a smoothed run alternates two sets and names the previous cycle's set as the old plan."""
+    import ctypes as C
+    import torch
+    from dart_planner_amd.capi import Params, SmootherParams
+    from dart_planner_amd.control.closed_loop import ClosedLoopMonteCarlo
+    calls = []
+    word = lambda a: (type(a).__name__ if isinstance(a, C.Structure) else tuple(a) if isinstance(a, C.Array) else "P" if isinstance(a, int) and a >= 4096 else a)
+    rec = lambda name, args: calls.append((name, [word(a) for a in args], list(args)))
+    monkeypatch.setattr(ops.lib, "call", lambda base, suf, *args, params=None: rec(f"{base}_{suf}", (params,) + args))
+    monkeypatch.setattr(ops.lib, "loop_call", lambda base, suf, *args: rec(f"{base}_{suf}", args))
+    monkeypatch.setattr(ops.lib, "controller_reset", lambda *args: rec("controller_reset", args))
+    monkeypatch.setattr(ops.lib, "smoother_reset", lambda *args: rec("smoother_reset", args))
+    monkeypatch.setattr(ops.be, "empty", lambda shape, kind: torch.zeros(shape, dtype=ops.be._dt[kind]))
+    B, N, cycles, substeps, sim_dt = 2, 6, 3, 2, 0.01
+    mc = ClosedLoopMonteCarlo(ops, Params.reference_defaults(horizon=N), ControllerParams.from_config(co.ControllerConfig()), SimulatorParams.reference_defaults())
+    mp = SmootherParams.reference_defaults()
+    p0, v0, goal = torch.zeros(B, 3, dtype=torch.float64), torch.zeros(B, 3, dtype=torch.float64), torch.ones(B, 3, dtype=torch.float64)
+    wind = torch.ones(B, 3, dtype=torch.float64)
+    mppi = dict(n_samples=8, iters=1, sigma=1.0, temperature=5.0, seed=3)
+    runs = dict(run=lambda: mc.run(p0, v0, goal, cycles, substeps, sim_dt, wind=wind),
+                run_smoothed=lambda: mc.run(p0, v0, goal, cycles, substeps, sim_dt, wind=wind, smoother=mp),
+                run_fused=lambda: mc.run_fused(p0, v0, goal, cycles, substeps, sim_dt, wind=wind),
+                run_mppi=lambda: mc.run_mppi(p0, v0, goal, cycles, substeps, sim_dt, wind=wind, **mppi),
+                run_mppi_smoothed=lambda: mc.run_mppi(p0, v0, goal, cycles, substeps, sim_dt, wind=wind, smoother=mp, **mppi),
+                run_mppi_fused=lambda: mc.run_mppi_fused(p0, v0, goal, cycles, substeps, sim_dt, wind=wind, **mppi))
+    out, raw = {}, {}
+    for name, fn in runs.items():
+        del calls[:]
+        keep = fn()                                                           # (alive while the addresses are compared)
+        out[name] = [" ".join([c[0]] + [str(w) for w in c[1]]) for c in calls]
+        raw[name] = [(c[0], c[2]) for c in calls]
+        del keep
+    plan_of = lambda args, at: tuple(args[at + i] for i in (1, 3, 5, 7))      # the four addresses of a nine-argument plan group
+    loops = [plan_of(a, 5)[1:] for n, a in raw["run"] if n == "closed_loop_f64"]
+    assert len(loops) == cycles and len(set(loops)) == 1, "run() re-uses one set of plan tensors"
+    for name in ("run_smoothed", "run_mppi_smoothed"):
+        upd = [(plan_of(a, 3)[1:], plan_of(a, 12)[1:]) for n, a in raw[name] if n == "smoother_update_f64"]
+        flown = [plan_of(a, 6)[1:] for n, a in raw[name] if n == "closed_loop_smoothed_f64"]
+        assert len(upd) == len(flown) == cycles and upd[0][0] == (0, 0, 0)
+        for c in range(cycles):
+            assert flown[c] == upd[c][1] and (c == 0 or upd[c][0] == upd[c - 1][1]), (name, c)
+        if name == "run_smoothed":
+            assert upd[0][1] == upd[2][1] != upd[1][1], "a smoothed run alternates two sets of plan tensors"
+    return out
+
+
+# what record_launch_sequences gives for the six methods (written from a run of the commit before ClosedLoopMonteCarlo got its one _start / _actor)
+LAUNCH_SEQUENCES = {'run': ['controller_reset ControllerParams 2 P 0',
+         'solve_f64 Params 2 P P P 0 P P P 0 0 0 0',
+         'closed_loop_f64 ControllerParams SimulatorParams 2 2 0.01 6 P 0 P 54 P 54 P 18 P P P P P P P 3 -1 None 0 0 0 0 P 0',
+         'solve_f64 Params 2 P P P 0 P P P 0 0 0 0',
+         'closed_loop_f64 ControllerParams SimulatorParams 2 2 0.01 6 P 0 P 54 P 54 P 18 P P P P P P P 3 -1 None 0 0 0 0 P 0',
+         'solve_f64 Params 2 P P P 0 P P P 0 0 0 0',
+         'closed_loop_f64 ControllerParams SimulatorParams 2 2 0.01 6 P 0 P 54 P 54 P 18 P P P P P P P 3 -1 None 0 0 0 0 P 0'],
+ 'run_smoothed': ['controller_reset ControllerParams 2 P 0',
+                  'smoother_reset 2 P 0',
+                  'solve_f64 Params 2 P P P 0 P P P 0 0 0 0',
+                  'smoother_update_f64 SmootherParams 2 P 0 0 0 0 0 0 0 0 0 6 P 0 P 54 P 54 P 18 P 0',
+                  'closed_loop_smoothed_f64 SmootherParams ControllerParams SimulatorParams 2 2 0.01 6 P 0 P 54 P 54 P 18 P P P P P P P P 3 -1 None 0 0 0 0 0',
+                  'solve_f64 Params 2 P P P 0 P P P 0 0 0 0',
+                  'smoother_update_f64 SmootherParams 2 P 6 P 0 P 54 P 54 P 18 6 P 0 P 54 P 54 P 18 P 0',
+                  'closed_loop_smoothed_f64 SmootherParams ControllerParams SimulatorParams 2 2 0.01 6 P 0 P 54 P 54 P 18 P P P P P P P P 3 -1 None 0 0 0 0 0',
+                  'solve_f64 Params 2 P P P 0 P P P 0 0 0 0',
+                  'smoother_update_f64 SmootherParams 2 P 6 P 0 P 54 P 54 P 18 6 P 0 P 54 P 54 P 18 P 0',
+                  'closed_loop_smoothed_f64 SmootherParams ControllerParams SimulatorParams 2 2 0.01 6 P 0 P 54 P 54 P 18 P P P P P P P P 3 -1 None 0 0 0 0 0'],
+ 'run_fused': ['controller_reset ControllerParams 2 P 0', 'monte_carlo_f64 Params ControllerParams SimulatorParams 2 3 2 0.01 P P 3 P P P P P P 0 0 0 P 0'],
+ 'run_mppi': ['controller_reset ControllerParams 2 P 0',
+              'mppi_closed_loop_f64 Params ControllerParams SimulatorParams 2 1 2 0.01 0 6 8 1 1.0 5.0 3 0 0 P 0 0 0.0 P 3 P P P P P P P P P 0 0 0',
+              'mppi_closed_loop_f64 Params ControllerParams SimulatorParams 2 1 2 0.01 1 6 8 1 1.0 5.0 3 0 0 P 0 0 0.0 P 3 P P P P P P P P P 0 0 0',
+              'mppi_closed_loop_f64 Params ControllerParams SimulatorParams 2 1 2 0.01 2 6 8 1 1.0 5.0 3 0 0 P 0 0 0.0 P 3 P P P P P P P P P 0 0 0'],
+ 'run_mppi_smoothed': ['controller_reset ControllerParams 2 P 0',
+                       'smoother_reset 2 P 0',
+                       'mppi_closed_loop_f64 Params ControllerParams SimulatorParams 2 1 0 0.01 0 6 8 1 1.0 5.0 3 0 0 P 0 0 0.0 P 3 P P P P P P P P P P 0 0',
+                       'smoother_update_f64 SmootherParams 2 P 0 0 0 0 0 0 0 0 0 6 P 0 P 54 P 54 P 54 P 0',
+                       'closed_loop_smoothed_f64 SmootherParams ControllerParams SimulatorParams 2 2 0.01 6 P 0 P 54 P 54 P 54 P P P P P P P P 3 -1 None 0 0 0 0 0',
+                       'mppi_closed_loop_f64 Params ControllerParams SimulatorParams 2 1 0 0.01 1 6 8 1 1.0 5.0 3 0 0 P 0 0 0.0 P 3 P P P P P P P P P P 0 0',
+                       'smoother_update_f64 SmootherParams 2 P 6 P 0 P 54 P 54 P 54 6 P 0 P 54 P 54 P 54 P 0',
+                       'closed_loop_smoothed_f64 SmootherParams ControllerParams SimulatorParams 2 2 0.01 6 P 0 P 54 P 54 P 54 P P P P P P P P 3 -1 None 0 0 0 0 0',
+                       'mppi_closed_loop_f64 Params ControllerParams SimulatorParams 2 1 0 0.01 2 6 8 1 1.0 5.0 3 0 0 P 0 0 0.0 P 3 P P P P P P P P P P 0 0',
+                       'smoother_update_f64 SmootherParams 2 P 6 P 0 P 54 P 54 P 54 6 P 0 P 54 P 54 P 54 P 0',
+                       'closed_loop_smoothed_f64 SmootherParams ControllerParams SimulatorParams 2 2 0.01 6 P 0 P 54 P 54 P 54 P P P P P P P P 3 -1 None 0 0 0 0 0'],
+ 'run_mppi_fused': ['controller_reset ControllerParams 2 P 0', 'mppi_closed_loop_f64 Params ControllerParams SimulatorParams 2 3 2 0.01 0 6 8 1 1.0 5.0 3 0 0 P 0 0 0.0 P 3 P P P P P P P P P 0 0 0']}
+
+
+def check_launch_sequences(ops, monkeypatch):
+    got = record_launch_sequences(ops, monkeypatch)
+    assert sorted(got) == sorted(LAUNCH_SEQUENCES)
+    for name, want in LAUNCH_SEQUENCES.items():
+        assert got[name] == want, (name, [(i, g, w) for i, (g, w) in enumerate(zip(got[name], want)) if g != w], len(got[name]), len(want))
+
+
+def check_operand_rules(h, monkeypatch):
+    """Ops.closed_loop, control_plan, simulator_step, control, controller_attitude_torque and controller_desired_frame refuse, with a
+    ValueError and before any launch, a clock, controller record, wind, thrust or yaw operand of the wrong row count, the wrong dtype or
+    (clocks and records) the wrong width, and leave the in/out tensors bit for bit as they were.  B = 3 drones, a plan of N = 2 rows.
+    A wrongly sized buffer must only ever be rejected: the library's call is replaced by a failure for the length of this check, so a
+    missing rule shows as a failed test and never as a kernel striding over a short buffer."""
+    import pytest
+    ops = h.ops
+    B, N = 3, 2
+    dt_, other = h.dt, (np.float32 if h.dt == np.float64 else np.float64)
+    cp, sp = ops.lib.controller_default_params(), ops.lib.simulator_default_params()
+    state = ops.controller_state(cp, B)                                        # (the one launch of this check: a fresh record)
+
+    def no_launch(base, suf, *args):
+        raise AssertionError(f"se3mpc_{base}_{suf} was called with an operand that should have been refused")
+    monkeypatch.setattr(ops.lib, "loop_call", no_launch)
+    d = lambda a, ty=dt_: h.to_dev(np.ascontiguousarray(np.asarray(a).astype(ty)))
+    good = dict(state=state, time=d(np.zeros(B), np.float64), sample_time=d(np.zeros(B), np.float64), pos=d(np.zeros((B, 3))), vel=d(np.zeros((B, 3))),
+                att=d(np.zeros((B, 3))), omega=d(np.zeros((B, 3))), thrust=d(np.full(B, 9.0)), torque=d(np.zeros((B, 3))), wind=d(np.ones((B, 3))),
+                yaw=d(np.zeros(B)), yaw_rate=d(np.zeros(B)), current_yaw=d(np.zeros(B)), dpos=d(np.ones((B, 3))), dvel=d(np.zeros((B, 3))),
+                b3_des=d(np.tile([0.0, 0.0, 1.0], (B, 1))), yaw_vector=d(np.tile([1.0, 0.0, 0.0], (B, 1))))
+    ts, P = d(np.arange(N) * 0.1, np.float64), d(np.zeros((N, 3)))
+    clock_bad = lambda: [d(np.zeros(B + 1), np.float64), d(np.zeros(B), np.float32), d(np.zeros((B, 2)), np.float64)]          # rows, dtype, width
+    record_bad = lambda: [d(np.zeros((B + 1, 12)), np.float64), d(np.zeros((B, 12)), np.float32), d(np.zeros((B, 13)), np.float64)]
+    per_drone_bad = lambda: [d(np.zeros(B + 1)), d(np.zeros(B), other)]                                                         # rows, dtype
+    wind_bad = lambda: [d(np.ones((B + 1, 3))), d(np.ones((B, 3)), other), d(np.ones(3), other)]
+    calls = dict(
+        closed_loop=(lambda g: ops.closed_loop(cp, sp, g["state"], g["time"], g["pos"], g["vel"], g["att"], g["omega"], ts, P, nsteps=2, wind=g["wind"]),
+                     dict(time=clock_bad, state=record_bad, wind=wind_bad)),
+        control_plan=(lambda g: ops.control_plan(cp, g["state"], g["time"], g["sample_time"], g["pos"], g["vel"], g["att"], g["omega"], ts, P),
+                      dict(time=clock_bad, sample_time=clock_bad, state=record_bad)),
+        simulator_step=(lambda g: ops.simulator_step(sp, g["time"], g["pos"], g["vel"], g["att"], g["omega"], g["thrust"], g["torque"], 0.01, wind=g["wind"]),
+                        dict(time=clock_bad, thrust=per_drone_bad, wind=wind_bad)),
+        control=(lambda g: ops.control(cp, g["state"], g["time"], g["pos"], g["vel"], g["att"], g["omega"], g["dpos"], g["dvel"], None, g["yaw"], g["yaw_rate"]),
+                 dict(yaw=per_drone_bad, yaw_rate=per_drone_bad, time=clock_bad)),
+        controller_attitude_torque=(lambda g: ops.controller_attitude_torque(cp, g["state"], g["att"], g["omega"], g["b3_des"], g["yaw"], g["yaw_rate"]),
+                                    dict(yaw=per_drone_bad, yaw_rate=per_drone_bad)),
+        controller_desired_frame=(lambda g: ops.controller_desired_frame(cp, g["yaw_vector"], g["b3_des"], g["current_yaw"]), dict(current_yaw=per_drone_bad)))
+    before = {k: np.array(h.to_host(v)).tobytes() for k, v in good.items()}
+    cases = 0
+    for name, (fn, operands) in calls.items():
+        for operand, bad in operands.items():
+            for wrong in bad():
+                with pytest.raises(ValueError):
+                    fn(dict(good, **{operand: wrong}))
+                cases += 1
+    assert cases == 3 * 3 + 3 * 3 + (3 + 2 + 3) + (2 + 2 + 3) + 4 + 2
+    for k, v in good.items():
+        assert np.array(h.to_host(v)).tobytes() == before[k], k

@@ -380,9 +380,10 @@ def check_monte_carlo_option(h, B=5, N=8, cycles=3, substeps=10):
     assert np.all(np.isfinite(h.to_host(m2["pos"]))) and np.allclose(h.to_host(m2["time"]), 2 * substeps * sim_dt) and m2["clearance"] is None
     assert np.all(h.to_host(m2["smoother_state"])[:, 24] >= 1)
     # the same two cycles by hand, the plan's three blocks (plan_last (B, 3, N, 3) = P, V, A) copied out into tensors of their own
-    pos, vel, att, om, time, st, U = mc._mppi_start(p0, v0, None)
+    st, sm, (time, pos, vel, att, om) = mc._start(p0, v0, mp)
+    U = mc._mppi_start(p0, None)
     sh = mc.resolve_shift(substeps, sim_dt, None)
-    sm, old = ops.smoother_state(B), None
+    old = None
     for c in range(2):
         out = ops.mppi_closed_loop(prm, mc.controller, mc.simulator, st, time, pos, vel, att, om, goal, U, 1, 0, sim_dt, 64, 2, 1.0, 1.0, seed=3, cycle_base=c,
                                    shift=sh, want_plan=True, want_clearance=False)

@@ -392,3 +392,20 @@ def test_plan_host_entry_point(emu_ops):
     z = np.zeros((B, 3), np.float32); X = np.zeros((B, 270), np.float32); info = np.zeros((B,), INFO_DTYPE); done = np.zeros(1, np.uint64)
     assert lib.call_status("plan_host", "f32", B, z.ctypes.data, z.ctypes.data, z.ctypes.data, 0, X.ctypes.data, info.ctypes.data, 0, 0, 0, 0,
                            done.ctypes.data, 1, 1e6, None, params=prm) == -3
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32])
+def test_plan_operand_rules_of_every_entry_point(emu_ops, dt):
+    cc.check_plan_rules(harness(emu_ops, dt))
+
+
+def test_monte_carlo_methods_make_the_same_library_calls(emu_ops, monkeypatch):
+    """ClosedLoopMonteCarlo.run / run(smoother=) / run_fused / run_mppi / run_mppi(smoother=) / run_mppi_fused: entry points, order and scalar
+    arguments against the literal lists of tests/controller_checks.py.  Host logic: no GPU twin."""
+    from numpy_backend import TorchCpuBackend
+    cc.check_launch_sequences(Ops(TorchCpuBackend(), emu_ops.lib), monkeypatch)
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32])
+def test_front_ends_refuse_wrong_operands_before_any_launch(emu_ops, dt, monkeypatch):
+    cc.check_operand_rules(harness(emu_ops, dt), monkeypatch)

@@ -476,3 +476,13 @@ def test_closed_loop_refuses_strides_that_leave_the_storage(gpu_ops):
         ops.closed_loop(cp, sp, st, t, z.clone(), z.clone(), z.clone(), z.clone(), ts, X, X[:, 3 * N:], acc, nsteps=2, strides=(9 * N, 9 * N, 9 * N))  # acc is 3N wide
     with pytest.raises(ValueError, match="storage"):
         ops.closed_loop(cp, sp, st, t, z.clone(), z.clone(), z.clone(), z.clone(), ts, X[:4], X[:, 3 * N:], acc, nsteps=2, strides=(19 * N, 9 * N, 3 * N))
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32])
+def test_plan_operand_rules_of_every_entry_point(gpu_ops, dt):
+    cc.check_plan_rules(harness(gpu_ops, dt))
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32])
+def test_front_ends_refuse_wrong_operands_before_any_launch(gpu_ops, dt, monkeypatch):
+    cc.check_operand_rules(harness(gpu_ops, dt), monkeypatch)

@@ -162,8 +162,77 @@ class SmootherParams(C.Structure):
         return type(self).reference_defaults(**{**{k: getattr(self, k) for k, _ in self._fields_}, **overrides})
 
 
+class MixerParams(C.Structure):
+    """struct se3mpc_mixer_params == MotorMixer.inverse_matrix / mixing_matrix (src/dart_planner/hardware/motor_mixer.py:379-398, :152-166),
+    the MotorParameters of motors 0..3 (src/dart_planner/hardware/motor_model.py:33-48), MotorMixingConfig's PWM limits (motor_mixer.py:64-66)
+    and the constants of the Pixhawk loop (hardware/pixhawk_interface.py:413, :473, :482).  All doubles."""
+    MOTOR_FIELDS = ("thrust_a", "thrust_b", "thrust_c", "pwm_min", "pwm_max", "pwm_idle", "torque_coefficient", "rpm_coefficient", "rpm_offset")
+    SCALAR_FIELDS = ("config_pwm_min", "config_pwm_max", "config_pwm_idle", "max_thrust", "body_rate_scale", "watchdog_threshold")
+    _fields_ = ([("inverse", C.c_double * 16), ("mixing", C.c_double * 16)] + [(n, C.c_double * 4) for n in MOTOR_FIELDS]
+                + [(n, C.c_double) for n in SCALAR_FIELDS])
+
+    @classmethod
+    def from_matrices(cls, B, inverse, motors, config_pwm_min=0.0, config_pwm_max=1.0, config_pwm_idle=0.1, max_thrust=10.0,
+                      body_rate_scale=2.0, watchdog_threshold=5.0) -> "MixerParams":
+        """B, inverse: 4 x 4 (mixing_matrix, inverse_matrix); motors: four objects with MotorParameters' attribute names (or dicts)."""
+        p = cls()
+        for name, m in (("mixing", B), ("inverse", inverse)):
+            flat = [float(v) for row in m for v in row]
+            if len(flat) != 16:
+                raise ValueError(f"{name}: a 4 x 4 matrix")
+            setattr(p, name, (C.c_double * 16)(*flat))
+        motors = list(motors)
+        if len(motors) != 4:
+            raise ValueError("motors: the parameters of motors 0..3")
+        for name in cls.MOTOR_FIELDS:
+            setattr(p, name, (C.c_double * 4)(*[float(m[name] if isinstance(m, dict) else getattr(m, name)) for m in motors]))
+        p.config_pwm_min, p.config_pwm_max, p.config_pwm_idle = float(config_pwm_min), float(config_pwm_max), float(config_pwm_idle)
+        p.max_thrust, p.body_rate_scale, p.watchdog_threshold = float(max_thrust), float(body_rate_scale), float(watchdog_threshold)
+        return p
+
+    @classmethod
+    def reference_defaults(cls, **overrides) -> "MixerParams":
+        """create_x_configuration_mixer(0.15) with create_default_motor_model() and the Pixhawk constants, computed here the way
+        se3mpc_mixer_default_params() does (the test-suite checks the two agree); B's inverse by Gauss-Jordan with partial pivoting."""
+        x = 0.15 * 0.707
+        px, py, dirs = (x, x, -x, -x), (-x, x, x, -x), (1.0, -1.0, 1.0, -1.0)
+        motor = dict(thrust_a=2.5, thrust_b=1.2, thrust_c=0.1, pwm_min=0.0, pwm_max=1.0, pwm_idle=0.1, torque_coefficient=1e-7,
+                     rpm_coefficient=8000.0, rpm_offset=500.0)
+        rpm = max(0.0, motor["rpm_coefficient"] * 1.0 + motor["rpm_offset"])
+        k_drag = max(0.0, motor["torque_coefficient"] * (rpm * rpm)) / max(0.0, (motor["thrust_a"] * 1.0 + motor["thrust_b"] * 1.0) + motor["thrust_c"])
+        Bm = [[1.0] * 4, list(py), list(px), [d * k_drag for d in dirs]]
+        a = [row[:] + [1.0 if i == j else 0.0 for j in range(4)] for i, row in enumerate(Bm)]
+        for k in range(4):
+            piv = max(range(k, 4), key=lambda i: abs(a[i][k]))
+            a[k], a[piv] = a[piv], a[k]
+            a[k] = [v / a[k][k] for v in a[k]]
+            for i in range(4):
+                if i != k:
+                    a[i] = [v - a[i][k] * w for v, w in zip(a[i], a[k])]
+        p = cls.from_matrices(Bm, [row[4:] for row in a], [motor] * 4)
+        return p.copy(**overrides) if overrides else p
+
+    def copy(self, **overrides) -> "MixerParams":
+        q = type(self)()
+        C.memmove(C.byref(q), C.byref(self), C.sizeof(type(self)))
+        for k, v in overrides.items():
+            if k not in dict(self._fields_):
+                raise AttributeError(f"se3mpc_mixer_params has no field {k!r}")
+            if k in self.SCALAR_FIELDS:
+                setattr(q, k, float(v))
+            else:
+                flat = [float(x) for x in (v if k in self.MOTOR_FIELDS else [x for row in v for x in row])]
+                setattr(q, k, (C.c_double * len(flat))(*flat))
+        return q
+
+
+assert C.sizeof(MixerParams) == 592       # static_assert of csrc/mixer_device.hpp
+
 CONTROLLER_STATE_WORDS = 12
 SMOOTHER_STATE_WORDS = 25
+MIXER_STATE_WORDS = 5
+# flag bits of se3mpc_mixer_mix_* (include/se3mpc.h)
+MIXER_NEGATIVE_THRUST, MIXER_NON_FINITE, MIXER_OVERRUN, MIXER_SATURATION_EVENT, MIXER_ALL_IDLE, MIXER_WATCHDOG = 1, 2, 4, 8, 16, 32
 
 _P = C.c_void_p
 _I = C.c_int
@@ -217,6 +286,7 @@ _VOXEL_PLAIN_API = {
 _CP = C.POINTER(ControllerParams)
 _SP = C.POINTER(SimulatorParams)
 _MP = C.POINTER(SmootherParams)
+_XP = C.POINTER(MixerParams)
 _LL = C.c_longlong
 _PLAN = [_I, _P, _LL, _P, _LL, _P, _LL, _P, _LL]            # N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA
 # consumer side of the contract: se3mpc_<base>_<suffix>(...)
@@ -234,6 +304,10 @@ _LOOP_TYPED_API = {
     "smoother_desired": [_MP, _I, _P, _P, _P] + _PLAN + [_P, _P, _P, _P],
     "closed_loop_smoothed": [_MP, _CP, _SP, _I, _I, _D] + _PLAN + [_P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, C.POINTER(C.c_double * 3),
                              _P, _P, _P, _P, _P],
+    "mixer_mix": [_XP, _I, _P, _P, _P, _P, _P, _P, _P],
+    "mixer_readback": [_XP, _I, _P, _P, _LL, _P, _P, _P, _P, _P, _P],
+    "closed_loop_actuated": [_MP, _CP, _SP, _XP, _I, _I, _D] + _PLAN + [_P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _LL, _I,
+                             C.POINTER(C.c_double * 3), _P, _P, _P, _P, _P, _P, _P],
     "monte_carlo": [_PP, _CP, _SP, _I, _I, _I, _D, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mppi_closed_loop": [_PP, _CP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _D, _P, _LL,
                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
@@ -244,6 +318,8 @@ _PLAIN_API = {
     "se3mpc_controller_reset": (C.c_int, [_CP, _I, _P, _P]),
     "se3mpc_smoother_default_params": (C.c_int, [_MP]),
     "se3mpc_smoother_reset": (C.c_int, [_I, _P, _P]),
+    "se3mpc_mixer_default_params": (C.c_int, [_XP]),
+    "se3mpc_mixer_reset": (C.c_int, [_I, _P, _P]),
     "se3mpc_abi_version": (C.c_int, []),
     "se3mpc_last_error": (C.c_char_p, []),
     "se3mpc_device_count": (C.c_int, []),
@@ -394,13 +470,21 @@ class Library:
     def smoother_reset(self, B: int, state: int, stream: int) -> None:
         self._check("se3mpc_smoother_reset", self._dll.se3mpc_smoother_reset(B, state, stream))
 
+    def mixer_default_params(self) -> MixerParams:
+        p = MixerParams()
+        self._check("se3mpc_mixer_default_params", self._dll.se3mpc_mixer_default_params(C.byref(p)))
+        return p
+
+    def mixer_reset(self, B: int, state: int, stream: int) -> None:
+        self._check("se3mpc_mixer_reset", self._dll.se3mpc_mixer_reset(B, state, stream))
+
     def loop_call(self, base: str, suffix: str, *args) -> None:
         """se3mpc_control_<suffix> / se3mpc_closed_loop_<suffix>; struct arguments are passed by reference here."""
-        a = [C.byref(x) if isinstance(x, (ControllerParams, SimulatorParams, SmootherParams, Params)) else x for x in args]
+        a = [C.byref(x) if isinstance(x, _STRUCTS) else x for x in args]
         self._check(f"se3mpc_{base}_{suffix}", getattr(self._dll, f"se3mpc_{base}_{suffix}")(*a))
 
     def loop_status(self, base: str, suffix: str, *args) -> int:
-        a = [C.byref(x) if isinstance(x, (ControllerParams, SimulatorParams, SmootherParams, Params)) else x for x in args]
+        a = [C.byref(x) if isinstance(x, _STRUCTS) else x for x in args]
         return getattr(self._dll, f"se3mpc_{base}_{suffix}")(*a)
 
     # -- voxel map ----------------------------------------------------------------------------
@@ -422,6 +506,7 @@ class Library:
             raise Se3mpcError(name, rc, self.last_error() if rc == -6 else "")
 
 
+_STRUCTS = (ControllerParams, SimulatorParams, SmootherParams, MixerParams, Params)
 _default: Optional[Library] = None
 
 

@@ -8,12 +8,14 @@ arithmetic, no copies between the two; the only host work per cycle is the N pla
 ``run_mppi`` / ``run_mppi_fused`` close the same loop with MPPI as the planner (``se3mpc_mppi_closed_loop_*``: plan, control and simulate
 inside one kernel, the plan handed over in LDS).  ``run(..., smoother=SmootherParams)`` / ``run_mppi(..., smoother=...)`` put the reference's
 TrajectorySmoother between plan and controller, as its edge loop does (edge/main_improved.py:96-152): plan -> ``se3mpc_smoother_update_*`` ->
-``se3mpc_closed_loop_smoothed_*`` per cycle; the one-launch forms do not have it.
+``se3mpc_closed_loop_smoothed_*`` per cycle; the one-launch forms do not have it.  ``mixer=MixerParams`` (with or without the
+smoother) puts the reference's MotorMixer and motor model behind the controller: the act phase becomes ``se3mpc_closed_loop_actuated_*`` and the
+simulator flies under what the motors deliver, ``motor_health`` scaling each motor's thrust.
 """
 import math
 from typing import Optional
 
-from ..capi import ControllerParams, Params, SimulatorParams, SmootherParams
+from ..capi import ControllerParams, MixerParams, Params, SimulatorParams, SmootherParams
 
 
 class ClosedLoopMonteCarlo:
@@ -33,6 +35,17 @@ class ClosedLoopMonteCarlo:
             raise ValueError(f"{what} has no trajectory smoother (the one-launch kernels keep one plan per drone on the chip, DESIGN.md 5.7c): "
                              "use run / run_mppi with smoother=")
 
+    @staticmethod
+    def _no_mixer(mixer, motor_health, what: str) -> None:
+        if mixer is not None or motor_health is not None:
+            raise ValueError(f"{what} has no motor mixer (the one-launch kernels hand the simulator the commanded wrench, DESIGN.md 5.7d): "
+                             "use run / run_mppi with mixer=")
+
+    @staticmethod
+    def _mixer_option(mixer, motor_health) -> None:
+        if motor_health is not None and mixer is None:
+            raise ValueError("motor_health scales what the mixer's motors deliver: it needs mixer=")
+
     def _start(self, p0, v0, smoother=None):
         """Every method's start: -> st (fresh controller records), sm (fresh smoother records, None without a smoother) and the drones'
         flight state fl = (time, pos, vel, att, omega): zero clocks, clones of p0 / v0, zero attitudes and body rates."""
@@ -45,18 +58,23 @@ class ClosedLoopMonteCarlo:
         st = ops.controller_state(self.controller, B)
         return st, (ops.smoother_state(B) if smoother is not None else None), (time, pos, vel, att, om)
 
-    def _actor(self, smoother, st, sm, fl, strides, substeps: int, sim_dt: float, wind):
+    def _actor(self, smoother, st, sm, fl, strides, substeps: int, sim_dt: float, wind, mixer=None, mx=None, motor_health=None):
         """-> act(plan, log): `substeps` control + simulator steps of every drone against plan = (stamps, P, V, A) with `strides`, as one
         ``se3mpc_closed_loop_*`` launch -- or, with a smoother, update_trajectory against the plan of the call before (None at first; the
-        caller keeps that plan's tensors alive and unchanged until then) and one ``se3mpc_closed_loop_smoothed_*`` launch."""
+        caller keeps that plan's tensors alive and unchanged until then) and one ``se3mpc_closed_loop_smoothed_*`` launch.  With a mixer
+        (records mx) the launch is ``se3mpc_closed_loop_actuated_*`` in either case."""
         ops, old = self.ops, [None]
 
         def act(plan, log: bool = False):
+            if smoother is not None:
+                ops.smoother_update(smoother, sm, fl[0], *plan, strides=strides, old=old[0], old_strides=strides)   # the wall clock of update_trajectory = the drones' clocks
+                old[0] = plan
+            if mixer is not None:
+                return ops.closed_loop_actuated(mixer, self.controller, self.simulator, st, mx, *fl, *plan, nsteps=substeps, sim_dt=sim_dt, strides=strides,
+                                                smoother=smoother, smoother_state=sm, motor_health=motor_health, wind=wind, log=log)
             if smoother is None:
                 return ops.closed_loop(self.controller, self.simulator, st, *fl, *plan, nsteps=substeps, sim_dt=sim_dt, strides=strides, wind=wind,
                                        stop_at_plan_end=False, log=log)
-            ops.smoother_update(smoother, sm, fl[0], *plan, strides=strides, old=old[0], old_strides=strides)   # the wall clock of update_trajectory = the drones' clocks
-            old[0] = plan
             return ops.closed_loop_smoothed(smoother, self.controller, self.simulator, st, sm, *fl, *plan, nsteps=substeps, sim_dt=sim_dt,
                                             strides=strides, wind=wind, log=log)
         return act
@@ -64,23 +82,30 @@ class ClosedLoopMonteCarlo:
     @staticmethod
     def _result(st, sm, fl, **more):
         time, pos, vel, att, om = fl
+        mx = more.pop("mixer_state", None)
         res = dict(pos=pos, vel=vel, att=att, omega=om, time=time, controller_state=st, **more)
         if sm is not None:
             res["smoother_state"] = sm
+        if mx is not None:
+            res["mixer_state"] = mx
         return res
 
     def run(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, wind=None, log: bool = False,
-            smoother: Optional[SmootherParams] = None):
+            smoother: Optional[SmootherParams] = None, mixer: Optional[MixerParams] = None, motor_health=None):
         """p0, v0, goal: (B, 3) device tensors (float32 or float64: the precision of the whole loop); wind: None, (3,) or (B, 3) newtons.
         smoother: None, or the parameters of the reference's TrajectorySmoother: every fresh plan then goes through update_trajectory
         (against the previous cycle's plan, so the plan tensors alternate between two sets) and every control step takes its target from
-        get_desired_state.  -> dict(pos, vel, att, omega (B, 3), time (B,), controller_state (B, 12), logs = [(solve outputs, closed-loop
-        outputs)] if log[, smoother_state (B, 25)])."""
+        get_desired_state.  mixer: None, or the parameters of the reference's MotorMixer and motor model: the controller's command goes
+        through mix_commands and the simulator runs under the wrench the motors deliver; motor_health: None, (4,) or (B, 4) factors on
+        each motor's thrust (needs `mixer`).  -> dict(pos, vel, att, omega (B, 3), time (B,), controller_state (B, 12), logs = [(solve
+        outputs, closed-loop outputs)] if log[, smoother_state (B, 25)][, mixer_state (B, 5)])."""
         import torch
         ops, prm = self.ops, self.params
         N = prm.horizon
+        self._mixer_option(mixer, motor_health)
         st, sm, fl = self._start(p0, v0, smoother)
-        act = self._actor(smoother, st, sm, fl, (9 * N, 9 * N, 3 * N), substeps, sim_dt, wind)
+        mx = ops.mixer_state(p0.shape[0]) if mixer is not None else None
+        act = self._actor(smoother, st, sm, fl, (9 * N, 9 * N, 3 * N), substeps, sim_dt, wind, mixer, mx, motor_health)
         k = torch.arange(N, dtype=torch.float64, device=ops.be.device)
         logs = []
         # without logs every cycle writes the same plan tensors again (the closed-loop launch of a cycle is ordered before the next solve); a
@@ -93,14 +118,16 @@ class ClosedLoopMonteCarlo:
             out = act(((c * substeps * sim_dt) + k * prm.dt, X, X[:, 3 * N:], sol["accelerations"]), log)
             if log:
                 logs.append((sol, out))
-        return self._result(st, sm, fl, logs=logs)
+        return self._result(st, sm, fl, logs=logs, mixer_state=mx)
 
-    def run_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, wind=None, want_last_plan: bool = False, smoother=None):
+    def run_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, wind=None, want_last_plan: bool = False, smoother=None,
+                  mixer=None, motor_health=None):
         """The same Monte-Carlo in ONE launch (``se3mpc_monte_carlo_*``: every cycle's solve and control / simulator steps inside one kernel,
         each drone paying only for its own slow solves instead of waiting, 2 x `cycles` times, at a kernel boundary for the slowest drone of
         the batch).  Same code, same bits as :meth:`run`.  One host synchronise at the end reads the overflow counter; if a solve needed more
         L-BFGS memory than the launch's LDS image holds (never with the reference's options) the run is repeated by :meth:`run`."""
         self._no_smoother(smoother, "run_fused")
+        self._no_mixer(mixer, motor_health, "run_fused")
         ops = self.ops
         st, sm, fl = self._start(p0, v0)
         out = ops.monte_carlo(self.params, self.controller, self.simulator, st, *fl, goal, cycles, substeps, sim_dt, wind=wind,
@@ -129,7 +156,7 @@ class ClosedLoopMonteCarlo:
 
     def run_mppi(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
                  seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None, nominal=None,
-                 log: bool = False, smoother: Optional[SmootherParams] = None):
+                 log: bool = False, smoother: Optional[SmootherParams] = None, mixer: Optional[MixerParams] = None, motor_health=None):
         """The receding-horizon Monte-Carlo with MPPI as the planner (``se3mpc_mppi_closed_loop_*``), one call per planning cycle: each
         cycle runs `iters` MPPI iterations of `n_samples` samples from the drone's own state on its nominal thrust sequence (hover, or
         `nominal` (B, N, 3)), hands the plan to the controller on the chip, takes `substeps` control + simulator steps and moves the
@@ -141,15 +168,19 @@ class ClosedLoopMonteCarlo:
         |pos - c| - r (None without spheres); logs = [dict(plan_last, trace, cost)] per cycle if `log`.
         smoother: None, or the parameters of the reference's TrajectorySmoother: each cycle is then the planner alone
         (``se3mpc_mppi_closed_loop_*`` with no simulator steps), update_trajectory against the previous cycle's plan and `substeps` steps of
-        ``se3mpc_closed_loop_smoothed_*``; clearance is None (only the fused act phase measures it), smoother_state (B, 25) is added."""
+        ``se3mpc_closed_loop_smoothed_*``; clearance is None (only the fused act phase measures it), smoother_state (B, 25) is added.
+        mixer, motor_health: as in :meth:`run`; the act phase is then ``se3mpc_closed_loop_actuated_*`` on the handed-over plan, with or
+        without the smoother (clearance None likewise), and mixer_state (B, 5) is added."""
         import torch
         ops, prm = self.ops, self.params
         B, N = p0.shape[0], prm.horizon
-        smoothed = smoother is not None
+        self._mixer_option(mixer, motor_health)
+        smoothed = smoother is not None or mixer is not None        # the act phase is a launch of its own
         st, sm, fl = self._start(p0, v0, smoother)
+        mx = ops.mixer_state(B) if mixer is not None else None
         U = self._mppi_start(p0, nominal)
         sh = self.resolve_shift(substeps, sim_dt, shift)
-        act = self._actor(smoother, st, sm, fl, (9 * N, 9 * N, 9 * N), substeps, sim_dt, wind)
+        act = self._actor(smoother, st, sm, fl, (9 * N, 9 * N, 9 * N), substeps, sim_dt, wind, mixer, mx, motor_health)
         k = torch.arange(N, dtype=torch.float64, device=ops.be.device) if smoothed else None
         logs, traces, out, clr = [], [], None, None
         for c in range(cycles):
@@ -165,11 +196,11 @@ class ClosedLoopMonteCarlo:
             if log:
                 logs.append(dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"]))
         trace = torch.cat(traces, dim=1) if traces else torch.zeros(B, 0, max(int(iters), 0), dtype=p0.dtype, device=ops.be.device)
-        return self._result(st, sm, fl, logs=logs, U=U, cost=None if out is None else out["cost"], trace=trace, clearance=clr)
+        return self._result(st, sm, fl, logs=logs, U=U, cost=None if out is None else out["cost"], trace=trace, clearance=clr, mixer_state=mx)
 
     def run_mppi_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float,
                        temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None,
-                       nominal=None, log: bool = False, smoother=None):
+                       nominal=None, log: bool = False, smoother=None, mixer=None, motor_health=None):
         """:meth:`run_mppi` in ONE launch: every drone's `cycles` planning cycles inside one kernel, the plan never leaving the chip.  Same
         code, same bits as :meth:`run_mppi`, same arguments and the same shift rule (shift=None: ``floor(substeps * sim_dt / params.dt +
         0.5)`` clipped to [0, N]).  `log` keeps the last cycle's plan only: logs = [dict(plan_last, trace, cost)] with one entry.
@@ -180,6 +211,7 @@ class ClosedLoopMonteCarlo:
         (float32) / two (float64) wavefronts per SIMD instead of four, and one lane per workgroup flies while the others wait): for thousands of
         drones drive the chain (``tools/gpu_probe_mppi_closed_loop.py``, ``chain_form``) unless the clearance output is what you need."""
         self._no_smoother(smoother, "run_mppi_fused")
+        self._no_mixer(mixer, motor_health, "run_mppi_fused")
         st, sm, fl = self._start(p0, v0)
         U = self._mppi_start(p0, nominal)
         sh = self.resolve_shift(substeps, sim_dt, shift)
@@ -189,12 +221,14 @@ class ClosedLoopMonteCarlo:
         logs = [dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"])] if log else []
         return self._result(st, sm, fl, logs=logs, U=U, cost=out["cost"], trace=out["trace"], clearance=out["clearance"])
 
-    def capture(self, B: int, dtype, cycles: int, substeps: int, sim_dt: float, with_wind: bool = True, smoother=None):
+    def capture(self, B: int, dtype, cycles: int, substeps: int, sim_dt: float, with_wind: bool = True, smoother=None, mixer=None,
+                motor_health=None):
         """The whole Monte-Carlo (2 x `cycles` kernel launches + the plan stamps) captured ONCE into a hipGraph; each call of the
         returned function copies new initial conditions into the graph's static inputs, replays it and returns the static outputs
         (overwritten by the next call).  Removes the per-launch host cost (~30 us of Python + launch per call, 66 calls per run)."""
         import torch
         self._no_smoother(smoother, "capture")
+        self._no_mixer(mixer, motor_health, "capture")
         dev = self.ops.be.device
         static = dict(p0=torch.zeros(B, 3, dtype=dtype, device=dev), v0=torch.zeros(B, 3, dtype=dtype, device=dev),
                       goal=torch.zeros(B, 3, dtype=dtype, device=dev), wind=torch.zeros(B, 3, dtype=dtype, device=dev) if with_wind else None)

@@ -17,7 +17,7 @@ import ctypes as _C
 
 import numpy as np
 
-from .capi import (CONTROLLER_STATE_WORDS, SMOOTHER_STATE_WORDS, ControllerParams, Library, Params, SimulatorParams, SmootherParams, SolveInfo,
+from .capi import (CONTROLLER_STATE_WORDS, MIXER_STATE_WORDS, SMOOTHER_STATE_WORDS, ControllerParams, MixerParams, Library, Params, SimulatorParams, SmootherParams, SolveInfo,
                    get_library, SE3MPC_MAX_SPHERES)
 
 INFO_DTYPE = np.dtype([("fun", "<f8"), ("nit", "<i4"), ("nfev", "<i4"), ("status", "<i4"), ("task", "<i4")])
@@ -893,6 +893,100 @@ class Ops:
                            self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega), self.be.ptr(state), self.be.ptr(smoother_state),
                            self.be.ptr(wind), w_stride, gust_step, gust_vec, self.be.ptr(logs.get("log_state")), self.be.ptr(logs.get("log_cmd")),
                            self.be.ptr(logs.get("log_time")), self.be.ptr(logs.get("log_target")), self.be.stream())
+        return logs
+
+    # ------------------------------------------------------------------ MotorMixer and motor model (per-drone rows)
+    def _mixer_record(self, state, B):
+        self.be.check(state, "mixer state")
+        if tuple(state.shape) != (B, MIXER_STATE_WORDS) or self.be.suffix(state) != "f64":
+            raise ValueError(f"mixer state: float64 ({B}, {MIXER_STATE_WORDS})")
+
+    def _rows4(self, a, B, name, suf):
+        self.be.check(a, name)
+        if tuple(a.shape) != (B, 4) or self.be.suffix(a) != suf:
+            raise ValueError(f"{name}: expected ({B}, 4) {suf}, got {tuple(a.shape)}")
+
+    def _health(self, motor_health, B, suf) -> int:
+        """A motor_health operand: None, one (4,) row for all drones or (B, 4) rows, of the call's dtype -> its row stride."""
+        if motor_health is None:
+            return 0
+        self.be.check(motor_health, "motor_health")
+        if self.be.suffix(motor_health) != suf or tuple(motor_health.shape) not in ((4,), (B, 4)):
+            raise ValueError(f"motor_health: (4,) or ({B}, 4) {suf}, got {tuple(motor_health.shape)}")
+        return 4 if motor_health.ndim == 2 else 0
+
+    def mixer_state(self, B: int):
+        """Fresh mixer members for B drones (MotorMixer.__init__): float64 (B, 5) = saturation_events, last_motor_commands; all zero."""
+        st = self.be.empty((B, MIXER_STATE_WORDS), "f64")
+        self.lib.mixer_reset(B, self.be.ptr(st), self.be.stream())
+        return st
+
+    def mixer_mix(self, mp: MixerParams, thrust, torque, state=None, want_flags: bool = True, want_body_rate: bool = False):
+        """mix_commands for B drones: thrust (B,), torque (B, 3) -> dict(pwm (B, 4)[, flags int32 (B,)][, body_rate (B, 4) = (normalised
+        thrust, roll, pitch, yaw rate) of _convert_to_body_rate_cmd]).  `state`: None or the records float64 (B, 5), updated in place."""
+        B = thrust.shape[0]
+        suf = self.be.suffix(thrust)
+        self._per_drone(B, suf, thrust=thrust)
+        self._rows3(torque, B, "torque", suf)
+        if state is not None:
+            self._mixer_record(state, B)
+        out = dict(pwm=self.be.empty((B, 4), suf))
+        if want_flags:
+            out["flags"] = self.be.empty((B,), "i32")
+        if want_body_rate:
+            out["body_rate"] = self.be.empty((B, 4), suf)
+        self.lib.loop_call("mixer_mix", suf, mp, B, self.be.ptr(thrust), self.be.ptr(torque), self.be.ptr(state), self.be.ptr(out["pwm"]),
+                           self.be.ptr(out.get("flags")), self.be.ptr(out.get("body_rate")), self.be.stream())
+        return out
+
+    MIXER_READBACK = ("motor_thrust", "motor_torque", "motor_rpm", "allocation", "wrench")
+
+    def mixer_readback(self, mp: MixerParams, pwm, motor_health=None, want=MIXER_READBACK):
+        """What the motors do under pwm (B, 4): each (B, 4) of `want` -- motor_thrust (thrust_from_pwm times the motor's health),
+        motor_torque, motor_rpm, allocation (get_control_allocation: the inverse matrix on the motor thrusts) and wrench (B @ motor
+        thrusts = the realised (thrust, torque)).  motor_health: None (1), (4,) or (B, 4)."""
+        B = pwm.shape[0]
+        suf = self.be.suffix(pwm)
+        self._rows4(pwm, B, "pwm", suf)
+        h_stride = self._health(motor_health, B, suf)
+        unknown = [k for k in want if k not in self.MIXER_READBACK]
+        if unknown:
+            raise ValueError(f"mixer_readback: no output {unknown}")
+        out = {k: self.be.empty((B, 4), suf) for k in self.MIXER_READBACK if k in want}
+        self.lib.loop_call("mixer_readback", suf, mp, B, self.be.ptr(pwm), self.be.ptr(motor_health), h_stride,
+                           *[self.be.ptr(out.get(k)) for k in self.MIXER_READBACK], self.be.stream())
+        return out
+
+    def closed_loop_actuated(self, mp: MixerParams, cp: ControllerParams, sp: SimulatorParams, state, mixer_state, time, pos, vel, att, omega,
+                             timestamps, P, V=None, A=None, nsteps: int = 1, sim_dt: float = 0.01, strides=None, smoother: SmootherParams = None,
+                             smoother_state=None, motor_health=None, wind=None, gust=None, log: bool = False):
+        """`nsteps` x (desired state -> compute_control -> mix_commands -> the motors' wrench -> DroneSimulator.step) for B drones in ONE
+        launch: :meth:`closed_loop_smoothed` (with `smoother` and `smoother_state`) or the raw plan sample of :meth:`closed_loop` (without
+        both), with the simulator under what the motors deliver.  `mixer_state` (B, 5) is updated in place with the other records.
+        -> dict([log_state, log_cmd (the COMMAND), log_time, log_target, log_pwm (nsteps, B, 4), log_wrench (nsteps, B, 4)])."""
+        B = time.shape[0]
+        suf = self.be.suffix(pos)
+        self._drone_state(B, suf, pos, vel, att, omega)
+        self._clock(time, B, "time")
+        self._ctrl_state(state, B)
+        self._mixer_record(mixer_state, B)
+        if (smoother is None) != (smoother_state is None):
+            raise ValueError("closed_loop_actuated: smoother and smoother_state come together or not at all")
+        if smoother_state is not None:
+            self._smoother_record(smoother_state, B)
+        plan = self._plan_ptrs(B, suf, timestamps, P, V, A, strides)
+        h_stride = self._health(motor_health, B, suf)
+        w_stride = self._wind(wind, B, suf)
+        gust_step, gust_vec = self._gust(gust)
+        nsteps = int(nsteps)
+        logs = self._loop_logs(nsteps, B, suf, log, target=True)
+        if log:
+            logs.update(log_pwm=self.be.empty((nsteps, B, 4), suf), log_wrench=self.be.empty((nsteps, B, 4), suf))
+        self.lib.loop_call("closed_loop_actuated", suf, smoother, cp, sp, mp, B, nsteps, float(sim_dt), *plan, self.be.ptr(time), self.be.ptr(pos),
+                           self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega), self.be.ptr(state), self.be.ptr(smoother_state),
+                           self.be.ptr(mixer_state), self.be.ptr(motor_health), h_stride, self.be.ptr(wind), w_stride, gust_step, gust_vec,
+                           *[self.be.ptr(logs.get(k)) for k in ("log_state", "log_cmd", "log_time", "log_target", "log_pwm", "log_wrench")],
+                           self.be.stream())
         return logs
 
     # ------------------------------------------------------------------ problem layout

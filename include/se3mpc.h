@@ -704,6 +704,101 @@ int se3mpc_closed_loop_smoothed_f64(const se3mpc_smoother_params* mp, const se3m
                                     int gust_step, const double* gust_wind, double* log_state, double* log_cmd, double* log_time,
                                     double* log_target, void* stream);
 
+/* ------------------------------------------------------------------ MotorMixer and motor model
+ * The last arithmetic stage between the controller's (thrust, torque) and the actuators in both hardware back ends of the reference
+ * (hardware/pixhawk_interface.py:451-492, hardware/airsim_interface.py:157-191; "mixer.py" = src/dart_planner/hardware/motor_mixer.py,
+ * "model.py" = src/dart_planner/hardware/motor_model.py), one drone per lane, reproduced with its quirks: a motor thrust below the
+ * thrust curve's minimum asks for FULL PWM (model.py:250-252), the model clips to the MOTOR's limits before the mixer clips to the
+ * CONFIG's, so the saturation counter (mixer.py:213, np.allclose with rtol 1e-6) sees only what the second clip and the idle floor
+ * move, and get_control_allocation applies the INVERSE matrix to the motor thrusts (mixer.py:279). */
+
+/* MotorMixer.mixing_matrix / inverse_matrix (mixer.py:379-398, :152-166), the QuadraticMotorModel's MotorParameters of motors 0..3
+ * (model.py:33-48), MotorMixingConfig's PWM limits (mixer.py:64-66) and the constants of the Pixhawk loop.  All doubles. */
+typedef struct se3mpc_mixer_params {
+  double inverse[16];                          /* inverse_matrix, row-major: motor thrusts = inverse @ (T, tx, ty, tz)  (mixer.py:195) */
+  double mixing[16];                           /* B, row-major: (T, tx, ty, tz) = B @ motor thrusts; column i = (1, y_i, x_i, direction_i * k_drag_i) */
+  double thrust_a[4], thrust_b[4], thrust_c[4];   /* thrust = a pwm^2 + b pwm + c, newtons        (model.py:34-36) */
+  double pwm_min[4], pwm_max[4], pwm_idle[4];  /* each MOTOR's limits                             (model.py:46-48) */
+  double torque_coefficient[4];                /* torque = kQ rpm^2                               (model.py:39)    */
+  double rpm_coefficient[4], rpm_offset[4];    /* rpm = k pwm + offset                            (model.py:42-43) */
+  double config_pwm_min, config_pwm_max, config_pwm_idle;   /* the CONFIG's limits                (mixer.py:64-66) */
+  double max_thrust;                           /* normalised thrust = clip(thrust / max_thrust, 0, 1)   (pixhawk_interface.py:473) */
+  double body_rate_scale;                      /* rad/s per PWM unit                              (pixhawk_interface.py:482) */
+  double watchdog_threshold;                   /* saturation_events > this trips the watchdog     (pixhawk_interface.py:413) */
+} se3mpc_mixer_params;
+
+/* Mutable mixer members (mixer.py:144-145), SE3MPC_MIXER_STATE_WORDS doubles per drone: [0] saturation_events, [1..4]
+ * last_motor_commands. */
+#define SE3MPC_MIXER_STATE_WORDS 5
+
+/* Flag bits of se3mpc_mixer_mix_*: negative thrust clamped to 0 (mixer.py:187-189); a non-finite motor thrust (:198-199, the
+ * reference raises RuntimeError); a raw PWM above 1.1 * config_pwm_max (:205-206); saturation_events was incremented (:213-214); all
+ * motors at the config's idle although thrust > 0.2 (:218); saturation_events > watchdog_threshold after this call. */
+#define SE3MPC_MIXER_NEGATIVE_THRUST 1
+#define SE3MPC_MIXER_NON_FINITE 2
+#define SE3MPC_MIXER_OVERRUN 4
+#define SE3MPC_MIXER_SATURATION_EVENT 8
+#define SE3MPC_MIXER_ALL_IDLE 16
+#define SE3MPC_MIXER_WATCHDOG 32
+
+/* create_x_configuration_mixer(0.15) (mixer.py:401-423) with create_default_motor_model() (model.py:386-437) and the Pixhawk constants
+ * (max_thrust 10, rate scale 2, watchdog 5): B as mixer.py:379-398, its inverse by LU with partial pivoting on the host. */
+int se3mpc_mixer_default_params(se3mpc_mixer_params* out);
+/* MotorMixer.__init__ (mixer.py:144-145) for B drones: state = device double[B][5], all zero. */
+int se3mpc_mixer_reset(int B, double* state, void* stream);
+
+/* mix_commands (mixer.py:168-222, with _thrust_to_pwm :224-242, pwm_from_thrust model.py:219-258 and _saturate_pwm :244-260) for B
+ * drones: thrust [B] newtons, torque [B][3] -> pwm [B][4].  state: NULL or the records [B][5], read and updated (a drone with the
+ * non-finite flag gets NaN PWMs and its record is left as it is).  flags: NULL or int32 [B], the bits above (the watchdog bit needs
+ * `state`).  body_rate: NULL or [B][4] = _convert_to_body_rate_cmd (pixhawk_interface.py:473-487): (normalised thrust, roll, pitch,
+ * yaw rate).
+ * Argument rules of the mixer's entry points: NULL parameters or a NULL required operand: SE3MPC_ERR_NULL; B < 0, nsteps < 0, a
+ * negative stride, a plan se3mpc_closed_loop_smoothed_* rejects: SE3MPC_ERR_SHAPE; a non-finite field outside the two matrices
+ * (which may hold whatever the host's linear algebra gave for a singular B), non-finite sim_dt: SE3MPC_ERR_PARAM.  B = 0 and nsteps = 0 are no-ops.  Every rejected
+ * call sets se3mpc_last_error and launches nothing. */
+int se3mpc_mixer_mix_f32(const se3mpc_mixer_params* mp, int B, const float* thrust, const float* torque, double* state, float* pwm,
+                         int32_t* flags, float* body_rate, void* stream);
+int se3mpc_mixer_mix_f64(const se3mpc_mixer_params* mp, int B, const double* thrust, const double* torque, double* state, double* pwm,
+                         int32_t* flags, double* body_rate, void* stream);
+
+/* What the motors do under pwm [B][4] (any output may be NULL, each [B][4]): motor_thrust = thrust_from_pwm (model.py:166-190) times
+ * the motor's health, motor_torque = torque_from_pwm (:192-217), motor_rpm = rpm_from_pwm (:260-282), allocation =
+ * get_control_allocation (mixer.py:262-279: the INVERSE matrix on the motor thrusts, as the reference has it), wrench = B @ motor
+ * thrusts = the (thrust, torque) the vehicle receives -- the reference never forms it; a simulator behind the mixer needs it.
+ * motor_health: NULL (= 1) or rows of 4 factors at motor_health + b * health_stride (stride 0 = one row for all drones): the
+ * fault-injection operand; the mixer does not see it. */
+int se3mpc_mixer_readback_f32(const se3mpc_mixer_params* mp, int B, const float* pwm, const float* motor_health, long long health_stride,
+                              float* motor_thrust, float* motor_torque, float* motor_rpm, float* allocation, float* wrench,
+                              void* stream);
+int se3mpc_mixer_readback_f64(const se3mpc_mixer_params* mp, int B, const double* pwm, const double* motor_health,
+                              long long health_stride, double* motor_thrust, double* motor_torque, double* motor_rpm, double* allocation,
+                              double* wrench, void* stream);
+
+/* se3mpc_closed_loop_smoothed_* with the actuators behind the controller, `nsteps` times per drone in ONE launch:  target =
+ * get_desired_state(t, state) -- or, with smp and smoother_state BOTH NULL, the raw plan sample of se3mpc_closed_loop_* (then N >= 1);
+ * one of the two alone is SE3MPC_ERR_NULL --;  cmd = compute_control(state, target, yaw 0);  pwm = mix_commands(cmd);  wrench = B @
+ * (motor_health * thrust_from_pwm(pwm));  state = DroneSimulator.step(state, wrench, sim_dt).  mixer_state [B][5] in / out;
+ * motor_health, health_stride as se3mpc_mixer_readback_*.  log_cmd keeps the COMMANDED (thrust, torque); log_pwm, log_wrench
+ * [nsteps][B][4]: NULL or the PWMs and the realised (thrust, torque); log_target as se3mpc_closed_loop_smoothed_* in both forms.  The same
+ * bits as nsteps chained (se3mpc_smoother_desired_* + se3mpc_control_*, or se3mpc_control_plan_*) -> se3mpc_mixer_mix_* ->
+ * se3mpc_mixer_readback_* -> se3mpc_simulator_step_* launches. */
+int se3mpc_closed_loop_actuated_f32(const se3mpc_smoother_params* smp, const se3mpc_controller_params* cp,
+                                    const se3mpc_simulator_params* sp, const se3mpc_mixer_params* mp, int B, int nsteps, double sim_dt,
+                                    int N, const double* timestamps, long long ts_stride, const float* P, long long strideP,
+                                    const float* V, long long strideV, const float* A, long long strideA, double* time, float* pos,
+                                    float* vel, float* att, float* omega, double* state, double* smoother_state, double* mixer_state,
+                                    const float* motor_health, long long health_stride, const float* wind, long long wind_stride,
+                                    int gust_step, const double* gust_wind, float* log_state, float* log_cmd, double* log_time,
+                                    float* log_target, float* log_pwm, float* log_wrench, void* stream);
+int se3mpc_closed_loop_actuated_f64(const se3mpc_smoother_params* smp, const se3mpc_controller_params* cp,
+                                    const se3mpc_simulator_params* sp, const se3mpc_mixer_params* mp, int B, int nsteps, double sim_dt,
+                                    int N, const double* timestamps, long long ts_stride, const double* P, long long strideP,
+                                    const double* V, long long strideV, const double* A, long long strideA, double* time, double* pos,
+                                    double* vel, double* att, double* omega, double* state, double* smoother_state, double* mixer_state,
+                                    const double* motor_health, long long health_stride, const double* wind, long long wind_stride,
+                                    int gust_step, const double* gust_wind, double* log_state, double* log_cmd, double* log_time,
+                                    double* log_target, double* log_pwm, double* log_wrench, void* stream);
+
 /* The receding-horizon closed-loop Monte-Carlo of BASELINE config 5's named test shape (tests/test_monte_carlo_sim.py:24-72) in ONE
  * launch: for each of B drones, `cycles` times { se3mpc_solve_* from the drone's own (pos, vel) with the reference's cold start;
  * `substeps` x se3mpc_closed_loop_*'s step (plan sample -> compute_control -> DroneSimulator.step at sim_dt) against the fresh plan,

@@ -8,9 +8,11 @@ arithmetic, no copies between the two; the only host work per cycle is the N pla
 ``run_mppi`` / ``run_mppi_fused`` close the same loop with MPPI as the planner (``se3mpc_mppi_closed_loop_*``: plan, control and simulate
 inside one kernel, the plan handed over in LDS).  ``run(..., smoother=SmootherParams)`` / ``run_mppi(..., smoother=...)`` put the reference's
 TrajectorySmoother between plan and controller, as its edge loop does (edge/main_improved.py:96-152): plan -> ``se3mpc_smoother_update_*`` ->
-``se3mpc_closed_loop_smoothed_*`` per cycle; the one-launch forms do not have it.  ``mixer=MixerParams`` (with or without the
+``se3mpc_closed_loop_smoothed_*`` per cycle.  ``mixer=MixerParams`` (with or without the
 smoother) puts the reference's MotorMixer and motor model behind the controller: the act phase becomes ``se3mpc_closed_loop_actuated_*`` and the
-simulator flies under what the motors deliver, ``motor_health`` scaling each motor's thrust.
+simulator flies under what the motors deliver, ``motor_health`` scaling each motor's thrust.  ``run_fused_staged`` flies both
+stages inside the one-launch solver-based Monte-Carlo (``se3mpc_monte_carlo_staged_*``); ``run_fused``, ``run_mppi_fused`` and
+``capture`` do not have them.
 """
 import math
 from typing import Optional
@@ -135,6 +137,32 @@ class ClosedLoopMonteCarlo:
         if int(ops.be.to_host(out["overflowed"])[0]) != 0:
             return self.run(p0, v0, goal, cycles, substeps, sim_dt, wind=wind)
         return self._result(st, sm, fl, logs=[], last_plan=out if want_last_plan else None)
+
+    def run_fused_staged(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, wind=None, want_last_plan: bool = False,
+                         smoother: Optional[SmootherParams] = None, mixer: Optional[MixerParams] = None, motor_health=None):
+        """:meth:`run` with `smoother` and / or `mixer` (and `motor_health`) in ONE launch (``se3mpc_monte_carlo_staged_*``): every cycle's
+        solve, update_trajectory and control / mixer / simulator steps inside one kernel, where :meth:`run` makes three launches per cycle.
+        Same code, same bits and the same result keys as :meth:`run` (no logs), plus last_plan as :meth:`run_fused`; without both stages it
+        is :meth:`run_fused`.  The kernel keeps ONE plan per drone on the chip: update_trajectory reads the plan being followed only at the
+        drone's clock, so that one sample is taken before the next solve overwrites the plan -- which is also why a run
+        cannot be continued by a second call.  If a solve needed more L-BFGS memory than the launch's LDS image holds (never with the
+        reference's options) the run is repeated by :meth:`run`.
+
+        Measured on an MI355X (``profiles/monte_carlo_staged.json``; 4096 drones, 33 cycles x 15 steps, horizon 6, both stages):
+        4.16 ms (float32) / 5.40 ms (float64) against 3.90 / 4.72 ms for the 99 launches of :meth:`run` -- at this shape the one launch is 7 - 15 %
+        SLOWER (one lane per drone flies the act phase, which the two stages make the larger part of a cycle; the chain's act kernel flies 64
+        drones per wavefront).  For thousands of drones with the stages drive :meth:`run`; use this form for small batches, where the chain is
+        launch-bound, or where one enqueue is what you need."""
+        self._mixer_option(mixer, motor_health)
+        ops = self.ops
+        st, sm, fl = self._start(p0, v0, smoother)
+        mx = ops.mixer_state(p0.shape[0]) if mixer is not None else None
+        out = ops.monte_carlo_staged(self.params, self.controller, self.simulator, st, *fl, goal, cycles, substeps, sim_dt, wind=wind,
+                                     want_last_plan=want_last_plan, smoother=smoother, smoother_state=sm, mixer=mixer, mixer_state=mx,
+                                     motor_health=motor_health)
+        if int(ops.be.to_host(out["overflowed"])[0]) != 0:
+            return self.run(p0, v0, goal, cycles, substeps, sim_dt, wind=wind, smoother=smoother, mixer=mixer, motor_health=motor_health)
+        return self._result(st, sm, fl, logs=[], last_plan=out if want_last_plan else None, mixer_state=mx)
 
     def resolve_shift(self, substeps: int, sim_dt: float, shift: Optional[int] = None) -> int:
         """Rows the MPPI nominal moves forward per planning cycle.  None: the plan steps one act phase covers, rounded half up,

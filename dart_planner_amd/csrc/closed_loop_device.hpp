@@ -418,19 +418,28 @@ __device__ __forceinline__ void cursor_before_step(PlanCursor<R>& cur, double si
   if (!(sim_dt > 0.0)) cur.idx = 0;
 }
 
-// One flight step of one drone: the plan sampled at the drone's clock, the geometric controller on the sample with yaw = yaw rate = 0, the
-// simulator step under the command.  -> the command (th, tq).
+// The command of one flight step of one drone: the plan sampled at the drone's clock, the geometric controller on the sample with yaw = yaw
+// rate = 0.  -> the command (th, tq); target_row: null, or where the sample (pos, vel, acc) [9] is logged.
+template <typename R>
+__device__ __forceinline__ void flight_command(const CtrlDev<R>& c, CtrlRegs<R>& s, PlanCursor<R>& cur, int N, const double* ts, const R* P,
+                                               const R* V, const R* A, const R p[3], const R v[3], const R a[3], const R w[3], double t,
+                                               double sim_dt, R& th, R tq[3], R* target_row) {
+  R tg[9];
+  cursor_before_step(cur, sim_dt);
+  sample_plan<R>(t, N, ts, P, V, A, tg, tg + 3, tg + 6, cur);
+  if (target_row != nullptr) for (int i = 0; i < 9; ++i) target_row[i] = tg[i];
+  int fl;
+  control_step<R>(c, s, t, p, v, a, w, tg, tg + 3, tg + 6, (R)0, (R)0, th, tq, fl);
+}
+
+// One flight step of one drone: flight_command, the simulator step under the command.  -> the command (th, tq).
 // The step of se3mpc_closed_loop_* (through lane_loop), se3mpc_monte_carlo_* and se3mpc_mppi_closed_loop_* (through fly_steps): one
 // definition, hence the same bits.
 template <typename R>
 __device__ __forceinline__ void flight_step(const CtrlDev<R>& c, const SimDev<R>& m, CtrlRegs<R>& s, PlanCursor<R>& cur, int N,
                                             const double* ts, const R* P, const R* V, const R* A, R p[3], R v[3], R a[3], R w[3], double& t,
                                             R dt, double sim_dt, const R wd[3], R& th, R tq[3]) {
-  R tp[3], tv[3], ta[3];
-  cursor_before_step(cur, sim_dt);
-  sample_plan<R>(t, N, ts, P, V, A, tp, tv, ta, cur);
-  int fl;
-  control_step<R>(c, s, t, p, v, a, w, tp, tv, ta, (R)0, (R)0, th, tq, fl);
+  flight_command<R>(c, s, cur, N, ts, P, V, A, p, v, a, w, t, sim_dt, th, tq, (R*)nullptr);
   simulator_step<R>(m, p, v, a, w, t, th, tq, dt, sim_dt, wd);
 }
 
@@ -479,6 +488,42 @@ __device__ __forceinline__ void drone_store(const DroneBlock<R>& d, int b, R* __
   timeg[b] = *d.time;
   for (int i = 0; i < SE3MPC_CONTROLLER_STATE_WORDS; ++i) stateg[(size_t)b * SE3MPC_CONTROLLER_STATE_WORDS + i] = d.ctrl[i];
 }
+
+// LDS of one wavefront of the solver-based one-launch loops (monte_carlo.hip, monte_carlo_staged.hip) behind the solver's image: per drone
+// (group) a DroneBlock with G plan rows in the IO type (positions, velocities, accelerations as the solver stores them) -- G stamps, time, controller record (doubles), the plan [3][G][3], then pos, vel, att,
+// omega, wind (15 IO) -- and behind it, 16-byte aligned (mc_consts_offset), what the kernel keeps there: monte_carlo.hip the controller's and the
+// simulator's constants, parked in LDS too so that the ~50 scalar registers they would occupy as kernel arguments are free while the solver
+// runs (read back inside the act phase only); monte_carlo_staged.hip the records of its stages
+template <typename IO>
+__host__ __device__ constexpr size_t mc_plan_offset(int G) { return (size_t)(G + 1 + SE3MPC_CONTROLLER_STATE_WORDS) * sizeof(double); }
+template <typename IO>
+__host__ __device__ constexpr size_t mc_consts_offset(int G) { return (mc_plan_offset<IO>(G) + (size_t)(9 * G + 16) * sizeof(IO) + 15) / 16 * 16; }
+template <typename IO>
+__host__ __device__ constexpr size_t mc_group_bytes(int G) { return mc_consts_offset<IO>(G) + (sizeof(CtrlDev<IO>) + sizeof(SimDev<IO>) + 15) / 16 * 16; }
+
+template <typename IO>
+struct McBlock {
+  DroneBlock<IO> d;
+  CtrlDev<IO>* ctl;
+  SimDev<IO>* sim;
+};
+// Group grp's block.  Built again inside each phase: only `grp` stays live while the solver has the registers.
+template <typename IO, int G>
+__device__ __forceinline__ McBlock<IO> mc_block(unsigned char* lds_raw, size_t solver_lds, int grp) {
+  unsigned char* gb = lds_raw + solver_lds + (size_t)grp * mc_group_bytes<IO>(G);
+  McBlock<IO> b;
+  b.d = drone_block<IO>(gb, G, mc_plan_offset<IO>(G), mc_plan_offset<IO>(G) + (size_t)9 * G * sizeof(IO));
+  b.ctl = reinterpret_cast<CtrlDev<IO>*>(gb + mc_consts_offset<IO>(G));
+  b.sim = reinterpret_cast<SimDev<IO>*>(b.ctl + 1);
+  return b;
+}
+
+// Wavefronts per SIMD of the solver-based one-launch loops.  One (512 registers): the kernels are chains of dependent scalar recurrences -- a
+// second resident wavefront would only matter from 8192 x (G / 8) drones up -- and at the solver's 256-register budget the loop-invariant
+// constants the compiler hoists out of the cycle loop cost monte_carlo_kernel ~90 spilled registers.
+#ifndef SE3MPC_MC_WAVES
+#define SE3MPC_MC_WAVES 1
+#endif
 
 // One drone in registers: position, velocity, attitude, body rates, the wind on it and its clock.  Loaded from and stored to the global
 // [B][3] arrays and clocks (the one-drone-per-lane kernels; load_state alone where a kernel has no use for wind or clock) or a DroneBlock

@@ -104,30 +104,11 @@ closed_loop_actuated_kernel(SmoothDev<R> d, CtrlDev<R> c, SimDev<R> m, MixDev<R>
   PlanCursor<R> cur;
   cursor_reset(cur);
   lane_loop<R>(dr, b, B, nsteps, gust_step, gx, gy, gz, false, 0.0, log_state, log_cmd, log_time, [&](int step, R& th, R* tq) {
-    R tg[9];
-    cursor_before_step(cur, sim_dt);
-    if constexpr (SMOOTH) smoother_desired<R>(d, sm, smoother_state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS + 9, dr.t, dr.p, dr.v, N, ts, Pb, Vb, Ab, cur, tg);
-    else sample_plan<R>(dr.t, N, ts, Pb, Vb, Ab, tg, tg + 3, tg + 6, cur);
-    if (log_target != nullptr) {
-      R* lt = log_target + ((size_t)step * B + b) * 9;
-      for (int i = 0; i < 9; ++i) lt[i] = tg[i];
-    }
-    int fl;
-    control_step<R>(c, s, dr.t, dr.p, dr.v, dr.a, dr.w, tg, tg + 3, tg + 6, (R)0, (R)0, th, tq, fl);
-    R p[4], F[4], Q[4], rpm[4], w[4];
-    const int mf = mix_step<R>(x, mx, th, tq, p);                                 // pixhawk_interface.py:464
-    (void)mf;
-    motors_realised<R>(x, p, motor_health != nullptr ? health : (const R*)nullptr, F, Q, rpm);
-    realised_wrench<R>(x, F, w);
-    if (log_pwm != nullptr) {
-      R* lp = log_pwm + ((size_t)step * B + b) * 4;
-      for (int i = 0; i < 4; ++i) lp[i] = p[i];
-    }
-    if (log_wrench != nullptr) {
-      R* lw = log_wrench + ((size_t)step * B + b) * 4;
-      for (int i = 0; i < 4; ++i) lw[i] = w[i];
-    }
-    simulator_step<R>(m, dr.p, dr.v, dr.a, dr.w, dr.t, w[0], w + 1, dt, sim_dt, dr.wd);
+    const size_t row = (size_t)step * B + b;
+    actuated_step<R, SMOOTH>(d, c, m, x, sm, SMOOTH ? smoother_state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS + 9 : nullptr, s, mx,
+                             motor_health != nullptr ? health : (const R*)nullptr, cur, N, ts, Pb, Vb, Ab, dr.p, dr.v, dr.a, dr.w, dr.t, dt, sim_dt,
+                             dr.wd, th, tq, log_target != nullptr ? log_target + row * 9 : nullptr, log_pwm != nullptr ? log_pwm + row * 4 : nullptr,
+                             log_wrench != nullptr ? log_wrench + row * 4 : nullptr);
   });
   dr.store(b, pos, vel, att, omega, time);
   store_ctrl<R>(state + (size_t)b * SE3MPC_CONTROLLER_STATE_WORDS, s);

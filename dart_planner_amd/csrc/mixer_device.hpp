@@ -4,7 +4,7 @@
 // INCLUDE UNDER `#pragma clang fp contract(off)`: the `thrust <= 0` tests, the discriminant's sign, the allclose threshold of the saturation
 // counter, the overrun and all-idle tests compare against values NumPy forms without FMA (see mixer.hip).
 #pragma once
-#include "closed_loop_device.hpp"
+#include "smoother_device.hpp"
 
 static_assert(sizeof(se3mpc_mixer_params) == 592, "se3mpc_mixer_params is part of the C ABI (capi.py mirrors it)");
 
@@ -163,6 +163,29 @@ __device__ __forceinline__ void control_allocation(const MixDev<R>& d, const R F
 template <typename R>
 __device__ __forceinline__ void realised_wrench(const MixDev<R>& d, const R F[4], R out[4]) {
   for (int j = 0; j < 4; ++j) out[j] = row4(d.mix, j, F);
+}
+
+// One actuated step of one drone: the command (smoothed_command, or SMOOTH = false: flight_command on the raw plan sample -- d, sm and tr are
+// not read then), mix_commands (pixhawk_interface.py:464), what the motors deliver under the PWMs (health: null = 1), the simulator step under
+// THAT wrench.  -> the COMMAND (th, tq); target_row [9], pwm_row [4], wrench_row [4]: null, or where the step's target, PWMs and delivered
+// wrench are logged.
+// The step of se3mpc_closed_loop_actuated_* (through lane_loop) and of se3mpc_monte_carlo_staged_* with the mixer: one definition, hence the
+// same bits.  Left to the inliner, like control_step.
+template <typename R, bool SMOOTH>
+__device__ inline void actuated_step(const SmoothDev<R>& d, const CtrlDev<R>& c, const SimDev<R>& m, const MixDev<R>& x, SmoothRegs<R>& sm,
+                                     const double* tr, CtrlRegs<R>& s, MixRegs<R>& mx, const R* health, PlanCursor<R>& cur, int N, const double* ts,
+                                     const R* P, const R* V, const R* A, R p[3], R v[3], R a[3], R w[3], double& t, R dt, double sim_dt,
+                                     const R wd[3], R& th, R tq[3], R* target_row, R* pwm_row, R* wrench_row) {
+  if constexpr (SMOOTH) smoothed_command<R>(d, c, sm, tr, s, cur, N, ts, P, V, A, p, v, a, w, t, sim_dt, th, tq, target_row);
+  else flight_command<R>(c, s, cur, N, ts, P, V, A, p, v, a, w, t, sim_dt, th, tq, target_row);
+  R pw[4], F[4], Q[4], rpm[4], wr[4];
+  const int mf = mix_step<R>(x, mx, th, tq, pw);                                  // pixhawk_interface.py:464
+  (void)mf;
+  motors_realised<R>(x, pw, health, F, Q, rpm);
+  realised_wrench<R>(x, F, wr);
+  if (pwm_row != nullptr) for (int i = 0; i < 4; ++i) pwm_row[i] = pw[i];
+  if (wrench_row != nullptr) for (int i = 0; i < 4; ++i) wrench_row[i] = wr[i];
+  simulator_step<R>(m, p, v, a, w, t, wr[0], wr + 1, dt, sim_dt, wd);
 }
 
 static inline int check_mixer_params(const se3mpc_mixer_params* p) {

@@ -20,40 +20,7 @@
 
 namespace se3mpc {
 
-// LDS of one wavefront behind the solver's image: per drone (group) a DroneBlock with G plan rows in the IO type (positions, velocities,
-// accelerations as the solver stores them) -- G stamps, time, controller record (doubles), the plan [3][G][3], then pos, vel, att,
-// omega, wind (15 IO) -- and behind it, 16-byte aligned, the controller's and the simulator's constants: parked in LDS too, so that
-// the ~50 scalar registers they would occupy as kernel arguments are free while the solver runs (read back inside the act phase only)
-template <typename IO>
-__host__ __device__ constexpr size_t mc_plan_offset(int G) { return (size_t)(G + 1 + SE3MPC_CONTROLLER_STATE_WORDS) * sizeof(double); }
-template <typename IO>
-__host__ __device__ constexpr size_t mc_consts_offset(int G) { return (mc_plan_offset<IO>(G) + (size_t)(9 * G + 16) * sizeof(IO) + 15) / 16 * 16; }
-template <typename IO>
-__host__ __device__ constexpr size_t mc_group_bytes(int G) { return mc_consts_offset<IO>(G) + (sizeof(CtrlDev<IO>) + sizeof(SimDev<IO>) + 15) / 16 * 16; }
-
-template <typename IO>
-struct McBlock {
-  DroneBlock<IO> d;
-  CtrlDev<IO>* ctl;
-  SimDev<IO>* sim;
-};
-// Group grp's block.  Built again inside each phase: only `grp` stays live while the solver has the registers.
-template <typename IO, int G>
-__device__ __forceinline__ McBlock<IO> mc_block(unsigned char* lds_raw, size_t solver_lds, int grp) {
-  unsigned char* gb = lds_raw + solver_lds + (size_t)grp * mc_group_bytes<IO>(G);
-  McBlock<IO> b;
-  b.d = drone_block<IO>(gb, G, mc_plan_offset<IO>(G), mc_plan_offset<IO>(G) + (size_t)9 * G * sizeof(IO));
-  b.ctl = reinterpret_cast<CtrlDev<IO>*>(gb + mc_consts_offset<IO>(G));
-  b.sim = reinterpret_cast<SimDev<IO>*>(b.ctl + 1);
-  return b;
-}
-
-// One wavefront per SIMD (512 registers): the kernel is a chain of dependent scalar recurrences -- a second resident wavefront would
-// only matter from 8192 x (G / 8) drones up -- and at the solver's 256-register budget the loop-invariant constants the compiler hoists
-// out of the cycle loop cost this kernel ~90 spilled registers.
-#ifndef SE3MPC_MC_WAVES
-#define SE3MPC_MC_WAVES 1
-#endif
+// One wavefront per SIMD (SE3MPC_MC_WAVES, closed_loop_device.hpp)
 template <typename IO, int G>
 __global__ void __launch_bounds__(64, SE3MPC_MC_WAVES)
 monte_carlo_kernel(SolveDev q, CtrlDev<IO> ctl, SimDev<IO> sim, int B, int cycles, int substeps, double sim_dt, size_t solver_lds,

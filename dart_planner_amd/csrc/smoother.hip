@@ -76,16 +76,8 @@ closed_loop_smoothed_kernel(SmoothDev<R> d, CtrlDev<R> c, SimDev<R> m, int B, in
   PlanCursor<R> cur;
   cursor_reset(cur);
   lane_loop<R>(dr, b, B, nsteps, gust_step, gx, gy, gz, false, 0.0, log_state, log_cmd, log_time, [&](int step, R& th, R* tq) {
-    R x[9];
-    cursor_before_step(cur, sim_dt);
-    smoother_desired<R>(d, sm, smoother_state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS + 9, dr.t, dr.p, dr.v, N, ts, Pb, Vb, Ab, cur, x);   // main_improved.py:129
-    if (log_target != nullptr) {
-      R* lt = log_target + ((size_t)step * B + b) * 9;
-      for (int i = 0; i < 9; ++i) lt[i] = x[i];
-    }
-    int fl;
-    control_step<R>(c, s, dr.t, dr.p, dr.v, dr.a, dr.w, x, x + 3, x + 6, (R)0, (R)0, th, tq, fl);   // main_improved.py:134-136
-    simulator_step<R>(m, dr.p, dr.v, dr.a, dr.w, dr.t, th, tq, dt, sim_dt, dr.wd);                  // main_improved.py:139
+    smoothed_step<R>(d, c, m, sm, smoother_state + (size_t)b * SE3MPC_SMOOTHER_STATE_WORDS + 9, s, cur, N, ts, Pb, Vb, Ab, dr.p, dr.v, dr.a, dr.w,
+                     dr.t, dt, sim_dt, dr.wd, th, tq, log_target != nullptr ? log_target + ((size_t)step * B + b) * 9 : nullptr);
   });
   dr.store(b, pos, vel, att, omega, time);
   store_ctrl<R>(state + (size_t)b * SE3MPC_CONTROLLER_STATE_WORDS, s);

@@ -141,21 +141,30 @@ __device__ __forceinline__ void transition_state(const SmoothDev<R>& d, const do
   for (int i = 0; i < 3; ++i) { x[3 + i] = v[i]; x[6 + i] = a[i]; }
 }
 
-// update_trajectory (smoother.py:115-165) at the clock `now`; the OLD plan is sampled at (now, trajectory_start_time), the new one at (now, now).
+// update_trajectory (smoother.py:115-165) at the clock `now` in two parts, because its ONLY read of the plan being followed is one sample at
+// (now, trajectory_start_time): a loop that keeps one plan per drone takes that sample before the planner overwrites the plan and hands the
+// nine values to the second part (monte_carlo_staged.hip).
+// (a) smoother.py:134-140: the plan being followed at the clock `now` -> cur = (pos, vel, acc) [9].  Reads the record, changes nothing.
 template <typename R>
-__device__ __forceinline__ void smoother_update(const SmoothDev<R>& d, SmoothRegs<R>& s, double now, int N_old, const double* ts_old, const R* P_old,
-                                                const R* V_old, const R* A_old, int N_new, const double* ts_new, const R* P_new,
-                                                const R* V_new, const R* A_new, double* __restrict__ tr) {
+__device__ __forceinline__ void smoother_sample_followed(const SmoothRegs<R>& s, double now, int N_old, const double* ts_old, const R* P_old,
+                                                         const R* V_old, const R* A_old, R cur[9]) {
+  PlanCursor<R> c;
+  cursor_reset(c);
+  sample_plan_smoother<R>(now - s.trajectory_start, N_old, ts_old, P_old, V_old, A_old, cur, c);   // :134-140
+}
+// (b) the rest: the first-plan rule (`cur` is not read then), the new plan sampled at (now, now), the thresholds, the record.
+template <typename R>
+__device__ __forceinline__ void smoother_take_plan(const SmoothDev<R>& d, SmoothRegs<R>& s, double now, const R cur[9], int N_new,
+                                                   const double* ts_new, const R* P_new, const R* V_new, const R* A_new,
+                                                   double* __restrict__ tr) {
   s.last_cloud_update = now;                                                      // :123
   if (!(s.bits & SM_HAS_TRAJECTORY)) {                                            // :125-131 the first plan is taken as it stands
     s.bits = SM_HAS_TRAJECTORY;
     s.trajectory_start = now;
     return;
   }
-  R cur[9], nw[9];
+  R nw[9];
   PlanCursor<R> c;
-  cursor_reset(c);
-  sample_plan_smoother<R>(now - s.trajectory_start, N_old, ts_old, P_old, V_old, A_old, cur, c);   // :134-140
   cursor_reset(c);
   sample_plan_smoother<R>(now - now, N_new, ts_new, P_new, V_new, A_new, nw, c);                   // :143-145
   R dp[3], dv[3];
@@ -166,6 +175,15 @@ __device__ __forceinline__ void smoother_update(const SmoothDev<R>& d, SmoothReg
     for (int i = 0; i < 6; ++i) { tr[i] = (double)cur[i]; tr[6 + i] = (double)nw[i]; }   // :155-158
   }                                                                               // (a small difference leaves a running transition running)
   s.trajectory_start = now;                                                       // :165
+}
+// update_trajectory with both plans in memory: (a) for a drone that follows a plan, then (b).
+template <typename R>
+__device__ __forceinline__ void smoother_update(const SmoothDev<R>& d, SmoothRegs<R>& s, double now, int N_old, const double* ts_old, const R* P_old,
+                                                const R* V_old, const R* A_old, int N_new, const double* ts_new, const R* P_new,
+                                                const R* V_new, const R* A_new, double* __restrict__ tr) {
+  R cur[9];
+  if (s.bits & SM_HAS_TRAJECTORY) smoother_sample_followed<R>(s, now, N_old, ts_old, P_old, V_old, A_old, cur);
+  smoother_take_plan<R>(d, s, now, cur, N_new, ts_new, P_new, V_new, A_new, tr);
 }
 
 // get_desired_state (smoother.py:167-213) at the clock `now` for a drone at (pos, vel) -> x = (pos, vel, acc) and the branch code.
@@ -202,6 +220,34 @@ __device__ __forceinline__ int smoother_desired(const SmoothDev<R>& d, SmoothReg
   }
   for (int i = 0; i < 3; ++i) { x[i] = pos[i]; x[3 + i] = (R)0; x[6 + i] = (R)0; }   // :213
   return SB_NO_TRAJECTORY;
+}
+
+// The command of one smoothed step of one drone (edge/main_improved.py:129-136): get_desired_state at the drone's clock, the geometric
+// controller on it with yaw = yaw rate = 0.  -> the command (th, tq); target_row: null, or where the desired state [9] is logged.
+// flight_command (closed_loop_device.hpp) with the smoother in the sampler's place.  Left to the inliner, like control_step.
+template <typename R>
+__device__ inline void smoothed_command(const SmoothDev<R>& d, const CtrlDev<R>& c, SmoothRegs<R>& sm, const double* tr,
+                                                 CtrlRegs<R>& s, PlanCursor<R>& cur, int N, const double* ts, const R* P, const R* V, const R* A,
+                                                 const R p[3], const R v[3], const R a[3], const R w[3], double t, double sim_dt, R& th, R tq[3],
+                                                 R* target_row) {
+  R x[9];
+  cursor_before_step(cur, sim_dt);
+  smoother_desired<R>(d, sm, tr, t, p, v, N, ts, P, V, A, cur, x);                // main_improved.py:129
+  if (target_row != nullptr) for (int i = 0; i < 9; ++i) target_row[i] = x[i];
+  int fl;
+  control_step<R>(c, s, t, p, v, a, w, x, x + 3, x + 6, (R)0, (R)0, th, tq, fl);  // main_improved.py:134-136
+}
+
+// One smoothed step of one drone: smoothed_command, the simulator step under the command (main_improved.py:139).
+// The step of se3mpc_closed_loop_smoothed_* (through lane_loop) and of se3mpc_monte_carlo_staged_* with the smoother alone: one definition,
+// hence the same bits.
+template <typename R>
+__device__ inline void smoothed_step(const SmoothDev<R>& d, const CtrlDev<R>& c, const SimDev<R>& m, SmoothRegs<R>& sm,
+                                              const double* tr, CtrlRegs<R>& s, PlanCursor<R>& cur, int N, const double* ts,
+                                              const R* P, const R* V, const R* A, R p[3], R v[3], R a[3], R w[3], double& t, R dt, double sim_dt,
+                                              const R wd[3], R& th, R tq[3], R* target_row) {
+  smoothed_command<R>(d, c, sm, tr, s, cur, N, ts, P, V, A, p, v, a, w, t, sim_dt, th, tq, target_row);
+  simulator_step<R>(m, p, v, a, w, t, th, tq, dt, sim_dt, wd);
 }
 
 static inline int check_smoother_params(const se3mpc_smoother_params* p) {

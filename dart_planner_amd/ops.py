@@ -694,6 +694,41 @@ class Ops:
                            self.be.ptr(X), self.be.ptr(acc), self.be.ptr(info), self.be.ptr(over), self.be.stream())
         return dict(overflowed=over, x=X, accelerations=acc, info=info)
 
+    def monte_carlo_staged(self, params: Params, cp: ControllerParams, sp: SimulatorParams, state, time, pos, vel, att, omega, goal, cycles: int,
+                           substeps: int, sim_dt: float, wind=None, want_last_plan: bool = False, smoother: SmootherParams = None,
+                           smoother_state=None, mixer: MixerParams = None, mixer_state=None, motor_health=None):
+        """se3mpc_monte_carlo_staged_*: :meth:`monte_carlo` with the reference's TrajectorySmoother between plan and controller (`smoother`
+        and `smoother_state` (B, 25)) and / or its MotorMixer and motor model behind the controller (`mixer` and `mixer_state` (B, 5);
+        motor_health None, (4,) or (B, 4)), still ONE launch, in place on the records too.  Without both stages it is :meth:`monte_carlo`.
+        -> dict(overflowed, x, accelerations, info) as :meth:`monte_carlo`."""
+        B = pos.shape[0]
+        suf = self.be.suffix(pos)
+        self._drone_state(B, suf, pos, vel, att, omega, goal=goal)
+        self._ctrl_state(state, B)
+        self._clock(time, B, "time")
+        if (smoother is None) != (smoother_state is None):
+            raise ValueError("monte_carlo_staged: smoother and smoother_state come together or not at all")
+        if (mixer is None) != (mixer_state is None):
+            raise ValueError("monte_carlo_staged: mixer and mixer_state come together or not at all")
+        if motor_health is not None and mixer is None:
+            raise ValueError("monte_carlo_staged: motor_health needs mixer")
+        if smoother_state is not None:
+            self._smoother_record(smoother_state, B)
+        if mixer_state is not None:
+            self._mixer_record(mixer_state, B)
+        h_stride = self._health(motor_health, B, suf)
+        w_stride = self._wind(wind, B, suf)
+        N = params.horizon
+        over = self.be.empty((1,), "i32")
+        X = self.be.empty((B, 9 * N), suf) if want_last_plan else None
+        acc = self.be.empty((B, N, 3), suf) if want_last_plan else None
+        info = self.be.empty((B * INFO_DTYPE.itemsize,), "u8") if want_last_plan else None
+        self.lib.loop_call("monte_carlo_staged", suf, params, cp, sp, smoother, mixer, B, int(cycles), int(substeps), float(sim_dt), self.be.ptr(goal),
+                           self.be.ptr(wind), w_stride, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega),
+                           self.be.ptr(state), self.be.ptr(smoother_state), self.be.ptr(mixer_state), self.be.ptr(motor_health), h_stride,
+                           self.be.ptr(X), self.be.ptr(acc), self.be.ptr(info), self.be.ptr(over), self.be.stream())
+        return dict(overflowed=over, x=X, accelerations=acc, info=info)
+
     def mppi_closed_loop(self, params: Params, cp: ControllerParams, sp: SimulatorParams, state, time, pos, vel, att, omega, goal, U,
                          cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
                          seed: int = 0, cycle_base: int = 0, shift: int = 1, iter_base: int = 0, index_base: int = 0, spheres=None,

@@ -818,6 +818,33 @@ int se3mpc_monte_carlo_f64(const se3mpc_params* p, const se3mpc_controller_param
                            double* pos, double* vel, double* att, double* omega, double* state, double* X_last, double* acc_last,
                            se3mpc_solve_info* info_last, int32_t* overflowed, void* stream);
 
+/* se3mpc_monte_carlo_* with the reference's full edge loop per drone (edge/main_improved.py:96-152: plan -> TrajectorySmoother ->
+ * GeometricController -> MotorMixer and motors -> DroneSimulator), still in ONE launch: for each of B drones, `cycles` times { se3mpc_solve_*
+ * from the drone's own (pos, vel); with smp, se3mpc_smoother_update_* at the drone's clock against the plan of the cycle before (none in the
+ * first cycle, also for a record that says it has a trajectory: as old = NULL there); `substeps` x the step of
+ * se3mpc_closed_loop_actuated_* (with mp: desired state or raw plan sample -> compute_control -> mix_commands -> the motors' wrench under
+ * motor_health -> DroneSimulator.step) or of se3mpc_closed_loop_smoothed_* (without mp) }.  The same code as the entry points it fuses, hence
+ * the same bits as launching them in turn (dart_planner_amd/control/closed_loop.py, run with smoother= / mixer=).  Arguments as
+ * se3mpc_monte_carlo_*, and: smp, mp: each may be NULL = the stage is absent (both NULL: this IS se3mpc_monte_carlo_*); smoother_state
+ * [B][SE3MPC_SMOOTHER_STATE_WORDS], mixer_state [B][SE3MPC_MIXER_STATE_WORDS]: in / out; motor_health NULL (exactly 1) or rows of
+ * health_stride (0 = one shared row) of four factors on the motors' thrusts, as se3mpc_closed_loop_actuated_*.  The plan being followed
+ * does not leave the chip: a run cannot be continued by a second call.
+ * Argument rules, before the B == 0 no-op: everything se3mpc_monte_carlo_* rejects, with the same codes; smp and smoother_state come
+ * together, mp and mixer_state come together, motor_health needs mp (SE3MPC_ERR_NULL); health_stride < 0 (SE3MPC_ERR_SHAPE); smoother /
+ * mixer parameters that se3mpc_smoother_update_* / se3mpc_mixer_mix_* reject (SE3MPC_ERR_PARAM). */
+int se3mpc_monte_carlo_staged_f32(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp,
+                                  const se3mpc_smoother_params* smp, const se3mpc_mixer_params* mp, int B, int cycles, int substeps,
+                                  double sim_dt, const float* goal, const float* wind, long long wind_stride, double* time, float* pos,
+                                  float* vel, float* att, float* omega, double* state, double* smoother_state, double* mixer_state,
+                                  const float* motor_health, long long health_stride, float* X_last, float* acc_last,
+                                  se3mpc_solve_info* info_last, int32_t* overflowed, void* stream);
+int se3mpc_monte_carlo_staged_f64(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp,
+                                  const se3mpc_smoother_params* smp, const se3mpc_mixer_params* mp, int B, int cycles, int substeps,
+                                  double sim_dt, const double* goal, const double* wind, long long wind_stride, double* time, double* pos,
+                                  double* vel, double* att, double* omega, double* state, double* smoother_state, double* mixer_state,
+                                  const double* motor_health, long long health_stride, double* X_last, double* acc_last,
+                                  se3mpc_solve_info* info_last, int32_t* overflowed, void* stream);
+
 /* The receding-horizon closed-loop Monte-Carlo with se3mpc_mppi_* as its planner, in ONE launch (one workgroup of min(S, 256) lanes per
  * drone; no atomics, no workspace, no allocation, no synchronise).  Everything is in problem layout: goal [B][3] (input); time [B],
  * pos / vel / att / omega [B][3], state [B][SE3MPC_CONTROLLER_STATE_WORDS]: in / out as se3mpc_monte_carlo_*; wind, wind_stride as

@@ -312,6 +312,8 @@ _LOOP_TYPED_API = {
     "monte_carlo_staged": [_PP, _CP, _SP, _MP, _XP, _I, _I, _I, _D, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P],
     "mppi_closed_loop": [_PP, _CP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _D, _P, _LL,
                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mppi_closed_loop_staged": [_PP, _CP, _SP, _MP, _XP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I,
+                                _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P],
 }
 _PLAIN_API = {
     "se3mpc_controller_default_params": (C.c_int, [_CP]),

@@ -11,8 +11,9 @@ TrajectorySmoother between plan and controller, as its edge loop does (edge/main
 ``se3mpc_closed_loop_smoothed_*`` per cycle.  ``mixer=MixerParams`` (with or without the
 smoother) puts the reference's MotorMixer and motor model behind the controller: the act phase becomes ``se3mpc_closed_loop_actuated_*`` and the
 simulator flies under what the motors deliver, ``motor_health`` scaling each motor's thrust.  ``run_fused_staged`` flies both
-stages inside the one-launch solver-based Monte-Carlo (``se3mpc_monte_carlo_staged_*``); ``run_fused``, ``run_mppi_fused`` and
-``capture`` do not have them.
+stages inside the one-launch solver-based Monte-Carlo (``se3mpc_monte_carlo_staged_*``), ``run_mppi_fused_staged`` inside the
+one-launch MPPI Monte-Carlo, where the clearance to the spheres is measured too (``se3mpc_mppi_closed_loop_staged_*``, DESIGN.md 5.8d);
+``run_fused``, ``run_mppi_fused`` and ``capture`` do not have them.
 """
 import math
 from typing import Optional
@@ -248,6 +249,38 @@ class ClosedLoopMonteCarlo:
                                         obstacle_weight=obstacle_weight, wind=wind, want_plan=log)
         logs = [dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"])] if log else []
         return self._result(st, sm, fl, logs=logs, U=U, cost=out["cost"], trace=out["trace"], clearance=out["clearance"])
+
+    def run_mppi_fused_staged(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float,
+                              temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None,
+                              shift: Optional[int] = None, nominal=None, log: bool = False, smoother: Optional[SmootherParams] = None,
+                              mixer: Optional[MixerParams] = None, motor_health=None):
+        """:meth:`run_mppi` with `smoother` and / or `mixer` (and `motor_health`) in ONE launch (``se3mpc_mppi_closed_loop_staged_*``): every
+        cycle's MPPI iterations, update_trajectory and control / mixer / simulator steps inside one kernel, where :meth:`run_mppi` makes
+        three launches per cycle -- and with ``clearance`` (B,) filled in whenever there are spheres, which the chain cannot measure.  Same
+        code, same bits, same arguments, shift rule and result keys as :meth:`run_mppi`; `log` keeps the last cycle's plan only, as
+        :meth:`run_mppi_fused`; without both stages it is :meth:`run_mppi_fused`.  The kernel keeps ONE plan per drone on the chip:
+        update_trajectory reads the plan being followed only at the drone's clock, so that one sample is taken before the next plan
+        overwrites it; the sample comes back as ``followed`` (B, 9) with a smoother, and ``Ops.mppi_closed_loop_staged``
+        takes it to continue a run.
+
+        Which form at which batch size: not measured (``tools/gpu_probe_mppi_closed_loop_staged.py`` is the probe: 256 and 4096 drones, 256 samples,
+        8 iterations, N = 30, 16 spheres, 33 cycles x 15 steps, both stages, against the 99 launches of :meth:`run_mppi`).  What the neighbouring
+        forms measured suggests this one for small batches, where the chain is launch-bound, and :meth:`run_mppi` for
+        thousands of drones -- one lane per workgroup flies the act phase, and with both stages the MPPI phase runs at two (float32) / one
+        (float64) wavefront per SIMD -- unless the clearance, which only this form measures with the stages, or one enqueue is what you need."""
+        self._mixer_option(mixer, motor_health)
+        ops = self.ops
+        st, sm, fl = self._start(p0, v0, smoother)
+        mx = ops.mixer_state(p0.shape[0]) if mixer is not None else None
+        U = self._mppi_start(p0, nominal)
+        sh = self.resolve_shift(substeps, sim_dt, shift)
+        out = ops.mppi_closed_loop_staged(self.params, self.controller, self.simulator, st, *fl, goal, U, cycles, substeps, sim_dt, n_samples, iters,
+                                          sigma, temperature, seed=seed, cycle_base=0, shift=sh, spheres=spheres, obstacle_weight=obstacle_weight,
+                                          wind=wind, want_plan=log, smoother=smoother, smoother_state=sm, mixer=mixer, mixer_state=mx,
+                                          motor_health=motor_health)
+        logs = [dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"])] if log else []
+        more = dict(followed=out["followed"]) if smoother is not None else {}
+        return self._result(st, sm, fl, logs=logs, U=U, cost=out["cost"], trace=out["trace"], clearance=out["clearance"], mixer_state=mx, **more)
 
     def capture(self, B: int, dtype, cycles: int, substeps: int, sim_dt: float, with_wind: bool = True, smoother=None, mixer=None,
                 motor_health=None):

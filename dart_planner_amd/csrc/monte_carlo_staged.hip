@@ -14,109 +14,29 @@
 // (StagedLayout).  Without either stage the entry point IS se3mpc_monte_carlo_*.
 #include "solve_device.hpp"
 #pragma clang fp contract(off)
-#include "mixer_device.hpp"
+#include "staged_device.hpp"
 
 namespace se3mpc {
 
 // A drone's LDS block: the DroneBlock of monte_carlo.hip (stamps, clock, controller record, plan, state and wind) and behind it, at
-// mc_consts_offset, the smoother's and the mixer's records (doubles, as in memory), the four health factors and the nine parked values of
-// the plan being followed (IO).  A stage the variant does not have costs nothing.
+// mc_consts_offset, the stages' share (StagedRecords, staged_device.hpp): the smoother's and the mixer's records (doubles, as in memory), the
+// four health factors and the nine parked values of the plan being followed (IO).  A stage the variant does not have costs nothing.
 // All constants -- controller, simulator, smoother, mixer: 1.1 KB in float64 -- stay kernel arguments here: the act phase reads them as
 // scalars.  Parked in LDS as monte_carlo.hip parks the first two they come back as VECTOR registers that stay live across the step loop,
 // and the float64 variants with the smoother spilled (8 registers with the two stages' constants as arguments, 89 - 113 with none).
 template <typename IO, bool SMOOTH, bool MIX>
 struct StagedLayout {
-  static constexpr size_t kRecordDoubles = (SMOOTH ? SE3MPC_SMOOTHER_STATE_WORDS : 0) + (MIX ? SE3MPC_MIXER_STATE_WORDS : 0);
-  static constexpr size_t kValues = (MIX ? 4 : 0) + (SMOOTH ? 9 : 0);
   __host__ __device__ static constexpr size_t records_offset(int G) { return mc_consts_offset<IO>(G); }
-  __host__ __device__ static constexpr size_t values_offset(int G) { return records_offset(G) + kRecordDoubles * sizeof(double); }
-  __host__ __device__ static constexpr size_t group_bytes(int G) { return (values_offset(G) + kValues * sizeof(IO) + 15) / 16 * 16; }
+  __host__ __device__ static constexpr size_t group_bytes(int G) { return records_offset(G) + StagedRecords<IO, SMOOTH, MIX>::bytes(); }
 };
 
-template <typename IO>
-struct StagedBlock {
-  DroneBlock<IO> d;
-  double *srec, *mrec;     // smoother record [SE3MPC_SMOOTHER_STATE_WORDS], mixer record [SE3MPC_MIXER_STATE_WORDS]
-  IO *health, *parked;     // [4], [9]
-};
 // Group grp's block (pointers of a stage the variant does not have are null).  Built again inside each phase, as mc_block.
 template <typename IO, int G, bool SMOOTH, bool MIX>
 __device__ __forceinline__ StagedBlock<IO> staged_block(unsigned char* lds_raw, size_t solver_lds, int grp) {
   using L = StagedLayout<IO, SMOOTH, MIX>;
   unsigned char* gb = lds_raw + solver_lds + (size_t)grp * L::group_bytes(G);
-  StagedBlock<IO> b;
-  b.d = drone_block<IO>(gb, G, mc_plan_offset<IO>(G), mc_plan_offset<IO>(G) + (size_t)9 * G * sizeof(IO));
-  double* rec = reinterpret_cast<double*>(gb + L::records_offset(G));
-  b.srec = SMOOTH ? rec : nullptr;
-  b.mrec = MIX ? rec + (SMOOTH ? SE3MPC_SMOOTHER_STATE_WORDS : 0) : nullptr;
-  IO* val = reinterpret_cast<IO*>(gb + L::values_offset(G));
-  b.health = MIX ? val : nullptr;
-  b.parked = SMOOTH ? val + (MIX ? 4 : 0) : nullptr;
-  return b;
-}
-
-// Drone pb's stage records and health factors (null = 1) into its block.  Nothing is followed yet: the parked values
-// are sample_plan_smoother's zeros for a plan that is not there, which is what se3mpc_smoother_update_* reads through old = NULL.
-template <typename IO, bool SMOOTH, bool MIX>
-__device__ __forceinline__ void staged_load(const StagedBlock<IO>& b, int pb, const double* __restrict__ smootherg,
-                                            const double* __restrict__ mixerg, const IO* __restrict__ healthg, long long health_stride) {
-  if constexpr (SMOOTH) {
-    for (int i = 0; i < SE3MPC_SMOOTHER_STATE_WORDS; ++i) b.srec[i] = smootherg[(size_t)pb * SE3MPC_SMOOTHER_STATE_WORDS + i];
-    for (int i = 0; i < 9; ++i) b.parked[i] = (IO)0;
-  }
-  if constexpr (MIX) {
-    for (int i = 0; i < SE3MPC_MIXER_STATE_WORDS; ++i) b.mrec[i] = mixerg[(size_t)pb * SE3MPC_MIXER_STATE_WORDS + i];
-    for (int i = 0; i < 4; ++i) b.health[i] = healthg != nullptr ? healthg[(size_t)pb * health_stride + i] : (IO)1;
-  }
-}
-// ... and the records back
-template <typename IO, bool SMOOTH, bool MIX>
-__device__ __forceinline__ void staged_store(const StagedBlock<IO>& b, int pb, double* __restrict__ smootherg, double* __restrict__ mixerg) {
-  if constexpr (SMOOTH)
-    for (int i = 0; i < SE3MPC_SMOOTHER_STATE_WORDS; ++i) smootherg[(size_t)pb * SE3MPC_SMOOTHER_STATE_WORDS + i] = b.srec[i];
-  if constexpr (MIX)
-    for (int i = 0; i < SE3MPC_MIXER_STATE_WORDS; ++i) mixerg[(size_t)pb * SE3MPC_MIXER_STATE_WORDS + i] = b.mrec[i];
-}
-
-// The act phase of one cycle of the drone in block b, by ONE lane, against the N-row plan the solver has just handed over: with the smoother
-// update_trajectory's second part at the drone's clock (the first part's nine values are parked in the block), then `substeps` steps --
-// actuated_step with the mixer, smoothed_step without -- and, when another cycle follows (`again`), the sample of THIS plan at the clock the
-// next update_trajectory will run at.  has_health: false = the health operand was NULL (exactly 1, as se3mpc_closed_loop_actuated_*).
-template <typename IO, bool SMOOTH, bool MIX>
-__device__ __forceinline__ void staged_act(const StagedBlock<IO>& b, const CtrlDev<IO>& c, const SimDev<IO>& m, const SmoothDev<IO>& sd, const MixDev<IO>& x, int N, int substeps,
-                                           double sim_dt, bool has_health, bool again) {
-  static_assert(SMOOTH || MIX, "without a stage the act phase is fly_steps (monte_carlo.hip)");
-  const DroneBlock<IO>& d = b.d;
-  SmoothRegs<IO> sm;
-  MixRegs<IO> mx;
-  CtrlRegs<IO> s = load_ctrl<IO>(d.ctrl);
-  DroneRegs<IO> r;
-  r.load(d);
-  double* tr = SMOOTH ? b.srec + 9 : nullptr;
-  if constexpr (SMOOTH) {
-    sm = load_smooth<IO>(b.srec);
-    smoother_take_plan<IO>(sd, sm, r.t, b.parked, N, d.stamps, d.planP, d.planV, d.planA, tr);   // the wall clock of update_trajectory = the drone's clock
-  }
-  if constexpr (MIX) mx = load_mix<IO>(b.mrec);
-  const IO* health = MIX && has_health ? b.health : nullptr;
-  const IO dt = (IO)sim_dt;
-  PlanCursor<IO> cur;
-  cursor_reset(cur);
-  for (int step = 0; step < substeps; ++step) {
-    IO th, tq[3];
-    if constexpr (MIX)
-      actuated_step<IO, SMOOTH>(sd, c, m, x, sm, tr, s, mx, health, cur, N, d.stamps, d.planP, d.planV, d.planA, r.p, r.v, r.a, r.w, r.t, dt, sim_dt,
-                                r.wd, th, tq, nullptr, nullptr, nullptr);
-    else
-      smoothed_step<IO>(sd, c, m, sm, tr, s, cur, N, d.stamps, d.planP, d.planV, d.planA, r.p, r.v, r.a, r.w, r.t, dt, sim_dt, r.wd, th, tq, nullptr);
-  }
-  r.store(d);
-  store_ctrl<IO>(d.ctrl, s);
-  if constexpr (MIX) store_mix<IO>(b.mrec, mx);
-  if constexpr (SMOOTH) {
-    if (again) smoother_sample_followed<IO>(sm, r.t, N, d.stamps, d.planP, d.planV, d.planA, b.parked);
-    store_smooth<IO>(b.srec, sm);
-  }
+  return staged_block_at<IO, SMOOTH, MIX>(drone_block<IO>(gb, G, mc_plan_offset<IO>(G), mc_plan_offset<IO>(G) + (size_t)9 * G * sizeof(IO)),
+                                          gb + L::records_offset(G));
 }
 
 }  // namespace se3mpc
@@ -149,7 +69,7 @@ monte_carlo_staged_kernel(SolveDev q, CtrlDev<IO> ctl, SimDev<IO> sim, SmoothDev
   if (k == 0) {
     const StagedBlock<IO> blk = staged_block<IO, G, SMOOTH, MIX>(lds_raw, solver_lds, grp);
     drone_load<IO>(blk.d, pb, posg, velg, attg, omegag, windg, wind_stride, timeg, stateg);
-    staged_load<IO, SMOOTH, MIX>(blk, pb, smootherg, mixerg, healthg, health_stride);
+    staged_load<IO, SMOOTH, MIX>(blk, pb, smootherg, mixerg, healthg, health_stride, nullptr);
   }
   group_sync<G>();
   const IO* x0row = nullptr;               // every cycle re-plans from the reference's cold start
@@ -201,7 +121,7 @@ monte_carlo_staged_kernel(SolveDev q, CtrlDev<IO> ctl, SimDev<IO> sim, SmoothDev
   if (k == 0) {
     const StagedBlock<IO> blk = staged_block<IO, G, SMOOTH, MIX>(lds_raw, solver_lds, grp);
     drone_store<IO>(blk.d, pb, posg, velg, attg, omegag, timeg, stateg);
-    staged_store<IO, SMOOTH, MIX>(blk, pb, smootherg, mixerg);
+    staged_store<IO, SMOOTH, MIX>(blk, pb, smootherg, mixerg, nullptr);
   }
 }
 

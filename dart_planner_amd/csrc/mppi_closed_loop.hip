@@ -14,11 +14,10 @@
 #include "closed_loop_device.hpp"
 #pragma clang fp contract(fast)
 #include "mppi_device.hpp"
+#include "mppi_loop_device.hpp"
 
 namespace se3mpc {
 namespace mppi {
-
-constexpr int kPark = 64;     // simulator positions parked per clearance reduction (longer act phases run in chunks of this many steps)
 
 // Wavefronts per SIMD the kernel is compiled for, chosen from the ISA.  The act phase holds the geometric controller in
 // one lane's registers: at the planner's four wavefronts per SIMD (128 registers) the float kernel spills 9 registers and the double
@@ -28,25 +27,7 @@ struct LoopWaves { static constexpr int value = 3; };
 template <>
 struct LoopWaves<double> { static constexpr int value = 2; };
 
-// LDS behind the planner's image (bytes, 16-byte aligned regions): stamps [N] double | time [1] double | controller record
-// [SE3MPC_CONTROLLER_STATE_WORDS] double | plan P, V, A [3][N][3] R | pos, vel, att, omega, wind, goal, clearance [19] R | raw radii [K] R | parked positions
-// [kPark][3] R
-struct LoopLds {
-  size_t stamps, time, ctrl, plan, vec, rad, park, total;
-};
-__host__ __device__ inline LoopLds loop_lds_layout(int N, int K, int W, size_t esz) {
-  LoopLds x;
-  x.stamps = lds_layout(N, K, W, esz).total;
-  x.time = x.stamps + (size_t)N * 8;
-  x.ctrl = x.time + 8;
-  x.plan = align16(x.ctrl + (size_t)SE3MPC_CONTROLLER_STATE_WORDS * 8);
-  x.vec = align16(x.plan + (size_t)9 * N * esz);
-  x.rad = align16(x.vec + 19 * esz);
-  x.park = align16(x.rad + (size_t)K * esz);
-  x.total = align16(x.park + (size_t)3 * kPark * esz);
-  return x;
-}
-
+// (the LDS image behind the planner's: LoopLds, mppi_loop_device.hpp)
 template <typename R>
 __global__ void __launch_bounds__(kBlock, LoopWaves<R>::value)
 mppi_closed_loop_kernel(DevParams<R> q, CtrlDev<R> ctl, SimDev<R> sim, double plan_dt, int cycles, int substeps, double sim_dt, uint32_t cycle_base,
@@ -57,7 +38,7 @@ mppi_closed_loop_kernel(DevParams<R> q, CtrlDev<R> ctl, SimDev<R> sim, double pl
                         R* __restrict__ cost_out, R* __restrict__ trace, R* __restrict__ plan_last, R* __restrict__ clearance) {
   HIP_DYNAMIC_SHARED(unsigned char, lds_raw)
   const int N = q.N, rows = 3 * N, NT = (int)blockDim.x, W = NT / kWave;
-  const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int tid = (int)threadIdx.x, wave = tid / kWave;
   const int b = (int)blockIdx.x;
   const LoopLds X = loop_lds_layout(N, K, W, sizeof(R));
   const LdsView<R> l = lds_view<R>(lds_raw, lds_layout(N, K, W, sizeof(R)));
@@ -101,14 +82,7 @@ mppi_closed_loop_kernel(DevParams<R> q, CtrlDev<R> ctl, SimDev<R> sim, double pl
     // ---- hand over: the nominal's trajectory, row k = the state before step k
     if (tid == 0) {
       R p[3] = {c.p0[0], c.p0[1], c.p0[2]}, v[3] = {c.v0[0], c.v0[1], c.v0[2]};
-      for (int k = 0; k < N; ++k) {
-        R a3[3];
-        const R t[3] = {U[3 * k], U[3 * k + 1], U[3 * k + 2]};
-        for (int a = 0; a < 3; ++a) { d.planP[3 * k + a] = p[a]; d.planV[3 * k + a] = v[a]; }
-        roll_state_step(q, p, v, t, a3);
-        for (int a = 0; a < 3; ++a) d.planA[3 * k + a] = a3[a];
-        d.stamps[k] = plan_stamp((int)C, substeps, sim_dt, k, plan_dt);
-      }
+      hand_over_plan(q, p, v, U, d, N, (int)C, substeps, sim_dt, plan_dt);
     }
     // ---- act, in chunks of kPark steps: the first lane flies, then the workgroup measures the clearance of the positions it left
     int s0 = 0;
@@ -119,21 +93,7 @@ mppi_closed_loop_kernel(DevParams<R> q, CtrlDev<R> ctl, SimDev<R> sim, double pl
           if (want_clear) { park[3 * step] = p[0]; park[3 * step + 1] = p[1]; park[3 * step + 2] = p[2]; }
         });
       __syncthreads();
-      if (want_clear && n > 0) {
-        R ml = (R)__builtin_huge_val();
-        for (int i = tid; i < n * K; i += NT) {
-          const int step = i / K, j = i - step * K;
-          const R dx = park[3 * step] - sph[4 * j], dy = park[3 * step + 1] - sph[4 * j + 1], dz = park[3 * step + 2] - sph[4 * j + 2];
-          ml = fmin(ml, sqrt(dx * dx + dy * dy + dz * dz) - rad[j]);
-        }
-        const double wm = wave_min((double)ml);
-        if (lane == 0) l.red[wave] = wm;
-        __syncthreads();
-        double mc = l.red[0];
-        for (int w = 1; w < W; ++w) mc = fmin(mc, l.red[w]);
-        if (tid == 0) s_vec[18] = fmin(s_vec[18], (R)mc);
-        __syncthreads();
-      }
+      if (want_clear && n > 0) clearance_chunk(park, sph, rad, n, K, l.red, s_vec + 18);
       s0 += kPark;
     } while (s0 < substeps);
     if (last && plan_last != nullptr)

@@ -771,6 +771,67 @@ class Ops:
             trace = trace[:, :max(int(cycles), 0), :max(int(iters), 0)]
         return dict(U=U, cost=cost, trace=trace, plan_last=plan, clearance=clearance)
 
+    def mppi_closed_loop_staged(self, params: Params, cp: ControllerParams, sp: SimulatorParams, state, time, pos, vel, att, omega, goal, U,
+                                cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
+                                seed: int = 0, cycle_base: int = 0, shift: int = 1, iter_base: int = 0, index_base: int = 0, spheres=None,
+                                obstacle_weight: float = 0.0, wind=None, want_trace: bool = True, want_plan: bool = False, clearance=None,
+                                want_clearance: bool = True, smoother: SmootherParams = None, smoother_state=None, mixer: MixerParams = None,
+                                mixer_state=None, motor_health=None, followed=None):
+        """se3mpc_mppi_closed_loop_staged_*: :meth:`mppi_closed_loop` with the reference's TrajectorySmoother between plan and controller
+        (`smoother` and `smoother_state` (B, 25)) and / or its MotorMixer and motor model behind the controller (`mixer` and `mixer_state`
+        (B, 5); motor_health None, (4,) or (B, 4)), still ONE launch and still with the clearance, in place on the records too.  followed:
+        (B, 9) = (pos, vel, acc) of the plan each drone follows at the clock the next update_trajectory runs at, updated in place so that a
+        later call (with `cycle_base`) continues the run; None: zeros = nothing followed yet (with a smoother).  Without both stages it is
+        :meth:`mppi_closed_loop`.  -> what :meth:`mppi_closed_loop` returns, plus followed (None without a smoother)."""
+        B = pos.shape[0]
+        suf = self.be.suffix(pos)
+        N = params.horizon
+        self._drone_state(B, suf, pos, vel, att, omega, goal=goal)
+        self._ctrl_state(state, B)
+        self._clock(time, B, "time")
+        self.be.check(U, "U")
+        if tuple(U.shape) != (B, N, 3) or self.be.suffix(U) != suf:
+            raise ValueError(f"U: expected ({B}, {N}, 3) {suf}, got {tuple(U.shape)}")
+        if (smoother is None) != (smoother_state is None):
+            raise ValueError("mppi_closed_loop_staged: smoother and smoother_state come together or not at all")
+        if (mixer is None) != (mixer_state is None):
+            raise ValueError("mppi_closed_loop_staged: mixer and mixer_state come together or not at all")
+        if motor_health is not None and mixer is None:
+            raise ValueError("mppi_closed_loop_staged: motor_health needs mixer")
+        if smoother_state is not None:
+            self._smoother_record(smoother_state, B)
+        if mixer_state is not None:
+            self._mixer_record(mixer_state, B)
+        h_stride = self._health(motor_health, B, suf)
+        w_stride = self._wind(wind, B, suf)
+        if followed is not None:
+            self.be.check(followed, "followed")
+            if tuple(followed.shape) != (B, 9) or self.be.suffix(followed) != suf:
+                raise ValueError(f"followed: expected ({B}, 9) {suf}, got {tuple(followed.shape)}")
+        elif smoother is not None:
+            followed = self.be.empty((B, 9), suf)
+            followed[...] = 0.0
+        K = 0
+        if spheres is not None:
+            K = self._spheres(spheres, suf)
+        self._per_drone(B, suf, clearance=clearance)
+        if clearance is None and want_clearance and K:
+            clearance = self.be.empty((B,), suf)
+            clearance[...] = float("inf")
+        cost = self.be.empty((B,), suf)
+        trace = self.be.empty((B, max(int(cycles), 1), max(int(iters), 1)), suf) if want_trace else None
+        plan = self.be.empty((B, 3, N, 3), suf) if want_plan else None
+        self.lib.loop_call("mppi_closed_loop_staged", suf, params, cp, sp, smoother, mixer, B, int(cycles), int(substeps), float(sim_dt),
+                           int(cycle_base) & 0xFFFFFFFF, int(shift), int(n_samples), int(iters), float(sigma), float(temperature),
+                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(iter_base) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF, self.be.ptr(goal),
+                           self.be.ptr(spheres if K else None), K, float(obstacle_weight), self.be.ptr(wind), w_stride, self.be.ptr(time),
+                           self.be.ptr(pos), self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega), self.be.ptr(state), self.be.ptr(smoother_state),
+                           self.be.ptr(mixer_state), self.be.ptr(motor_health), h_stride, self.be.ptr(followed), self.be.ptr(U), self.be.ptr(cost),
+                           self.be.ptr(trace), self.be.ptr(plan), self.be.ptr(clearance), self.be.stream())
+        if trace is not None and (cycles <= 0 or iters <= 0):
+            trace = trace[:, :max(int(cycles), 0), :max(int(iters), 0)]
+        return dict(U=U, cost=cost, trace=trace, plan_last=plan, clearance=clearance, followed=followed)
+
     def controller_integral_update(self, cp: ControllerParams, state, vel_error, dt: float, saturation=None) -> None:
         """_update_integral_error(vel_error, dt, thrust_saturated, torque_saturated) (controller.py:536-564) for B drones, in place on
         `state`.  saturation: int32 (B,) bit 0 thrust, bits 1..3 torque x/y/z, or None."""

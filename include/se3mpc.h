@@ -880,6 +880,43 @@ int se3mpc_mppi_closed_loop_f64(const se3mpc_params* p, const se3mpc_controller_
                                 double* pos, double* vel, double* att, double* omega, double* state, double* U, double* cost, double* trace,
                                 double* plan_last, double* clearance, void* stream);
 
+/* se3mpc_mppi_closed_loop_* with the reference's full edge loop per drone (edge/main_improved.py:96-152: plan -> TrajectorySmoother
+ * (control/trajectory_smoother.py:115-213) -> GeometricController (control/geometric_controller.py:413-512) -> MotorMixer and motors
+ * (hardware/motor_mixer.py:168-222, hardware/motor_model.py:166-282) -> DroneSimulator (utils/drone_simulator.py:52-72)), still in ONE launch
+ * and still with the clearance: for each of B drones, `cycles` times { plan and hand over as se3mpc_mppi_closed_loop_*; with smp,
+ * se3mpc_smoother_update_* at the drone's clock against the plan of the cycle before; `substeps` x the step of se3mpc_closed_loop_actuated_*
+ * (with mp: desired state or raw plan sample -> compute_control -> mix_commands -> the motors' wrench under motor_health ->
+ * DroneSimulator.step) or of se3mpc_closed_loop_smoothed_* (without mp); clearance after every simulator step; warm start }.  The same code
+ * as the entry points it fuses, hence the same bits as launching them in turn (dart_planner_amd/control/closed_loop.py, run_mppi with
+ * smoother= / mixer=).  Arguments as se3mpc_mppi_closed_loop_*, and: smp, mp: each may be NULL = the stage is absent (both NULL: this IS
+ * se3mpc_mppi_closed_loop_*); smoother_state [B][SE3MPC_SMOOTHER_STATE_WORDS], mixer_state [B][SE3MPC_MIXER_STATE_WORDS]: in / out;
+ * motor_health NULL (exactly 1) or rows of health_stride (0 = one shared row) of four factors on the motors' thrusts, as
+ * se3mpc_closed_loop_actuated_*; followed [B][9] (with smp), in / out: (pos, vel, acc) of the plan each drone follows, sampled at the clock
+ * the next update_trajectory runs at -- the one value update_trajectory reads of the previous plan (trajectory_smoother.py:134-140), which
+ * stays on the chip.  Zeros = nothing followed yet (what se3mpc_smoother_update_* reads through old = NULL); the sample is stored after the
+ * last cycle too, so one call with cycles = C equals C calls with cycles = 1 and cycle_base = 0 .. C - 1 that carry followed, the records, U
+ * and clearance along, bit for bit.
+ * Argument rules: everything se3mpc_mppi_closed_loop_* rejects, with the same codes; smp and smoother_state come together, mp and
+ * mixer_state come together, motor_health needs mp (SE3MPC_ERR_NULL); health_stride < 0 (SE3MPC_ERR_SHAPE); smoother / mixer parameters that
+ * se3mpc_smoother_update_* / se3mpc_mixer_mix_* reject (SE3MPC_ERR_PARAM); after the B = 0 / cycles = 0 no-op: followed NULL with smp
+ * (SE3MPC_ERR_NULL). */
+int se3mpc_mppi_closed_loop_staged_f32(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp,
+                                       const se3mpc_smoother_params* smp, const se3mpc_mixer_params* mp, int B, int cycles, int substeps,
+                                       double sim_dt, uint32_t cycle_base, int shift, int S, int iters, double sigma, double temperature,
+                                       uint64_t seed, uint32_t iter_base, uint32_t index_base, const float* goal, const float* spheres, int K,
+                                       double obstacle_weight, const float* wind, long long wind_stride, double* time, float* pos, float* vel,
+                                       float* att, float* omega, double* state, double* smoother_state, double* mixer_state,
+                                       const float* motor_health, long long health_stride, float* followed, float* U, float* cost, float* trace,
+                                       float* plan_last, float* clearance, void* stream);
+int se3mpc_mppi_closed_loop_staged_f64(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp,
+                                       const se3mpc_smoother_params* smp, const se3mpc_mixer_params* mp, int B, int cycles, int substeps,
+                                       double sim_dt, uint32_t cycle_base, int shift, int S, int iters, double sigma, double temperature,
+                                       uint64_t seed, uint32_t iter_base, uint32_t index_base, const double* goal, const double* spheres, int K,
+                                       double obstacle_weight, const double* wind, long long wind_stride, double* time, double* pos, double* vel,
+                                       double* att, double* omega, double* state, double* smoother_state, double* mixer_state,
+                                       const double* motor_health, long long health_stride, double* followed, double* U, double* cost,
+                                       double* trace, double* plan_last, double* clearance, void* stream);
+
 /* ------------------------------------------------------------------ problem layout: [b][row]
  * The batched solve: replaces _solve_se3_mpc (planner.py:230-280) = cold start (or a caller
  * x0), box, scipy.optimize.minimize(method="L-BFGS-B", jac=..., bounds=..., maxiter, gtol,

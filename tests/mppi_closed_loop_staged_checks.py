@@ -1,0 +1,290 @@
+"""What the CPU (host emulation) and GPU suites share for se3mpc_mppi_closed_loop_staged_* / Ops.mppi_closed_loop_staged /
+ClosedLoopMonteCarlo.run_mppi_fused_staged: the one-launch closed-loop MPPI Monte-Carlo with the TrajectorySmoother and the MotorMixer inside
+must give the BITS of the chain it fuses (ClosedLoopMonteCarlo.run_mppi with smoother= / mixer=: se3mpc_mppi_closed_loop_* as the planner,
+se3mpc_smoother_update_*, se3mpc_closed_loop_smoothed_* / _actuated_* per cycle), and the clearance that chain cannot measure must agree with
+the positions the chain logs.  The yardstick is always the chain; its results are computed once per configuration and shared.
+
+The scene.  An act phase is 5 x 0.01 s, so a new plan (row 0 = the drone's own state) and the one being followed can only drift 1 m/s apart
+-- the default smoother's transition threshold -- under a model error of more than 20 m/s^2: the wind, which neither planner nor controller
+sees, is lateral with 40 - 55 N on the simulator's 1.5 kg (27 - 37 m/s^2, 1.3 - 1.8 m/s per act phase).  Margins of the non-vacuity check:
+the stages and the health factors must move the final positions by more than 1e-3 m, four decades above the float32 rounding of a position
+of a few metres (2.4e-7 m per operation, 20 steps)."""
+import numpy as np
+
+import monte_carlo_staged_checks as sc
+from monte_carlo_staged_checks import SMOOTHERS, STAGES, same_bits
+from dart_planner_amd.capi import Params, SmootherParams
+from dart_planner_amd.control.closed_loop import ClosedLoopMonteCarlo
+
+CYCLES, SUBSTEPS, SIM_DT, ITERS = 4, 5, 0.01, 2
+SHAPES = [(6, 5, 0, 64), (13, 4, 3, 256), (30, 3, 16, 512)]        # (N, B, K, S): one wavefront per workgroup; a full block; two sample passes and the 16 spheres of the probe's scene
+# The host emulation runs a 256-lane workgroup two decades slower than the device (50 s per run at the largest shape): the CPU suite sweeps every
+# variant at the smallest shape and at one like it with spheres, and flies the full block once; the GPU suite sweeps all of SHAPES.
+EMU_SHAPES = [SHAPES[0], (6, 4, 2, 64)]
+PLAN_DT, SIGMA, LAM, W_OBS, SEED = 0.1, 1.0, 50.0, 40.0, 17
+LONG_SUBSTEPS = 70                                                 # > kPark = 64: an act phase of two chunks
+STATE_KEYS = ("pos", "vel", "att", "omega", "time", "controller_state")
+PLAN_KEYS = ("U", "cost", "trace")
+MOVES = 1e-3                                                       # metres; see the module docstring
+
+
+def scene(B, K):
+    rng = np.random.default_rng(23)
+    p0 = rng.uniform(-1, 1, (B, 3)) + [0, 0, 2]
+    v0 = rng.normal(0, 0.2, (B, 3))
+    goal = rng.uniform(-3, 3, (B, 3)) + [0, 0, 2]
+    heading, force = rng.uniform(0, 2 * np.pi, B), rng.uniform(40, 55, B)
+    wind = np.stack([force * np.cos(heading), force * np.sin(heading), rng.normal(0, 1, B)], axis=1)
+    health = rng.uniform(0.6, 1.0, (B, 4))
+    spheres = np.concatenate([rng.uniform(-3, 3, (K, 3)) + [0, 0, 2], rng.uniform(0.2, 0.6, (K, 1))], axis=1)
+    return p0, v0, goal, wind, health, spheres
+
+
+def params(N):
+    return Params.reference_defaults(horizon=N, dt=PLAN_DT)
+
+
+def _operands(h, shape, stage, wind="rows", smoother="default", shift=None, substeps=SUBSTEPS, cycles=CYCLES):
+    """-> (mc, positional arguments, keyword arguments) of run_mppi / run_mppi_fused_staged for one configuration."""
+    N, B, K, S = shape
+    p0, v0, goal, w, hl, sph = (h.prob(a) for a in scene(B, K))
+    with_smoother, with_mixer, health = STAGES[stage] if stage is not None else (False, False, None)
+    mc = ClosedLoopMonteCarlo(h.ops, params(N))
+    kw = dict(seed=SEED, spheres=sph if K else None, obstacle_weight=W_OBS if K else 0.0, shift=shift,
+              wind={"rows": w, None: None, "shared": w[0].contiguous()}[wind],
+              smoother=SmootherParams.reference_defaults(**SMOOTHERS[smoother]) if with_smoother else None,
+              mixer=h.ops.lib.mixer_default_params() if with_mixer else None,
+              motor_health={"rows": hl, None: None, "shared": hl[0].contiguous()}[health])
+    return mc, (p0, v0, goal, cycles, substeps, SIM_DT, S, ITERS, SIGMA, LAM), kw
+
+
+def record_keys(stage):
+    with_smoother, with_mixer, _ = STAGES[stage] if stage is not None else (False, False, None)
+    return (("smoother_state",) if with_smoother else ()) + (("mixer_state",) if with_mixer else ())
+
+
+_chain = {}
+
+
+def chain(h, shape, stage, wind="rows", smoother="default", shift=None, substeps=SUBSTEPS):
+    """ClosedLoopMonteCarlo.run_mppi for the configuration, as host arrays (computed once)."""
+    key = (id(h.ops), np.dtype(h.dt).name, shape, stage, wind, smoother, shift, substeps)
+    if key not in _chain:
+        mc, args, kw = _operands(h, shape, stage, wind, smoother, shift, substeps)
+        out = mc.run_mppi(*args, **kw)
+        assert out["clearance"] is None or stage is None                           # the chain measures no clearance with a stage: why the feature exists
+        _chain[key] = {k: np.array(h.to_host(out[k])) for k in STATE_KEYS + PLAN_KEYS + record_keys(stage)}
+    return _chain[key]
+
+
+def check_equals_chain(h, shape, stage, wind="rows", smoother="default", shift=None, substeps=SUBSTEPS):
+    """run_mppi_fused_staged gives the bits of run_mppi: the drones' state, the clocks, every record, the nominal, the last cost and every
+    trace row -- and a clearance where there are spheres."""
+    ref = chain(h, shape, stage, wind, smoother, shift, substeps)
+    mc, args, kw = _operands(h, shape, stage, wind, smoother, shift, substeps)
+    got = mc.run_mppi_fused_staged(*args, **kw)
+    for key in ("smoother_state", "mixer_state"):
+        assert (key in got) == (key in record_keys(stage))
+    assert got["logs"] == []
+    what = f"{stage} wind={wind} smoother={smoother} shift={shift} substeps={substeps}"
+    for key in STATE_KEYS + PLAN_KEYS + record_keys(stage):
+        same_bits(h.to_host(got[key]), ref[key], f"{what}: {key}")
+    if shape[2]:
+        clr = h.to_host(got["clearance"])
+        assert clr.shape == (shape[1],) and np.isfinite(clr).all(), clr
+    else:
+        assert got["clearance"] is None
+
+
+def check_clearance(h, shape):
+    """The clearance of the one launch against the chain driven by hand with logs (se3mpc_mppi_closed_loop_* with no steps ->
+    se3mpc_smoother_update_* -> se3mpc_closed_loop_actuated_* with log_state): the running minimum of |pos - c_j| - r_j over the logged
+    positions in float64 NumPy, within 16 eps_R max(|pos - c_j| + r_j) -- the two evaluations differ only in the rounding and contraction of
+    one three-term sum of squares, a square root and a subtraction, each a few units of roundoff in R, and min is 1-Lipschitz.  The logged
+    flight itself ends in the one launch's final state, as bytes."""
+    import torch
+    N, B, K, S = shape
+    assert K > 0
+    mc, args, kw = _operands(h, shape, "both_health")
+    fused = mc.run_mppi_fused_staged(*args, **kw)
+    ops, prm = h.ops, mc.params
+    p0, v0, goal = args[:3]
+    pos, vel, att, om = p0.clone(), v0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)
+    time = h.to_dev(np.zeros(B))
+    st, sm, mx = ops.controller_state(mc.controller, B), ops.smoother_state(B), ops.mixer_state(B)
+    U = h.prob(np.tile([0.0, 0.0, prm.mass * prm.gravity], (B, N, 1)))
+    sh = mc.resolve_shift(SUBSTEPS, SIM_DT, None)
+    k = h.to_dev(np.arange(N, dtype=np.float64))
+    strides, old, visited, plans = (9 * N, 9 * N, 9 * N), None, [], []
+    for c in range(CYCLES):
+        out = ops.mppi_closed_loop(prm, mc.controller, mc.simulator, st, time, pos, vel, att, om, goal, U, 1, 0, SIM_DT, S, ITERS, SIGMA, LAM, seed=SEED,
+                                   cycle_base=c, shift=sh, spheres=kw["spheres"], obstacle_weight=kw["obstacle_weight"], wind=kw["wind"], want_plan=True,
+                                   want_clearance=False)
+        flat = out["plan_last"].view(B, 9 * N)
+        plan = ((c * SUBSTEPS * SIM_DT) + k * prm.dt, flat, flat[:, 3 * N:], flat[:, 6 * N:])
+        plans.append(plan)                                                          # (the previous plan stays alive while it is `old`)
+        ops.smoother_update(kw["smoother"], sm, time, *plan, strides=strides, old=old, old_strides=strides)
+        old = plan
+        logs = ops.closed_loop_actuated(kw["mixer"], mc.controller, mc.simulator, st, mx, time, pos, vel, att, om, *plan, nsteps=SUBSTEPS, sim_dt=SIM_DT,
+                                        strides=strides, smoother=kw["smoother"], smoother_state=sm, motor_health=kw["motor_health"], wind=kw["wind"],
+                                        log=True)
+        ls = h.to_host(logs["log_state"]).astype(np.float64)
+        visited += [ls[1:, :, :3], h.to_host(pos).astype(np.float64)[None]]          # row s = the state BEFORE step s: after every step = rows 1.. and the end
+    for key, dev in (("pos", pos), ("vel", vel), ("att", att), ("omega", om), ("time", time), ("controller_state", st), ("smoother_state", sm),
+                     ("mixer_state", mx), ("U", U)):
+        same_bits(h.to_host(fused[key]), h.to_host(dev), f"the logged flight ends where the one launch ends: {key}")
+    visited = np.concatenate(visited, axis=0)                                       # (CYCLES * SUBSTEPS, B, 3)
+    assert visited.shape == (CYCLES * SUBSTEPS, B, 3)
+    sph = h.to_host(kw["spheres"]).astype(np.float64)
+    dist = np.linalg.norm(visited[:, :, None, :] - sph[None, None, :, :3], axis=-1)  # (steps, B, K)
+    want = (dist - sph[:, 3]).min(axis=(0, 2))
+    bound = 16 * float(np.finfo(h.dt).eps) * float((dist + sph[:, 3]).max())
+    err = float(np.abs(h.to_host(fused["clearance"]).astype(np.float64) - want).max())
+    print(f"{shape} {np.dtype(h.dt).name}: clearance error {err:.3e} (bound {bound:.3e}), clearance {want}")
+    assert err <= bound, (err, bound)
+
+
+def check_without_stages(h, shape):
+    """No stage: run_mppi_fused_staged == run_mppi_fused as bytes, clearance included -- which pins the clearance code to the already
+    pinned kernel."""
+    mc, args, kw = _operands(h, shape, None)
+    for k in ("smoother", "mixer", "motor_health"):
+        assert kw.pop(k) is None
+    a = mc.run_mppi_fused(*args, log=True, **kw)
+    b = mc.run_mppi_fused_staged(*args, log=True, **kw)
+    assert "smoother_state" not in b and "mixer_state" not in b and "followed" not in b
+    for key in STATE_KEYS + PLAN_KEYS + (("clearance",) if shape[2] else ()):
+        same_bits(h.to_host(b[key]), h.to_host(a[key]), f"no stage: {key}")
+    if not shape[2]:
+        assert a["clearance"] is None and b["clearance"] is None
+    same_bits(h.to_host(b["logs"][0]["plan_last"]), h.to_host(a["logs"][0]["plan_last"]), "no stage: plan_last")
+
+
+def _fresh(h, shape, lo=0, hi=None):
+    """Operands of Ops.mppi_closed_loop_staged for drones [lo, hi) of the scene, both stages, one health row per drone."""
+    import torch
+    N, B, K, S = shape
+    hi = B if hi is None else hi
+    n = hi - lo
+    p0, v0, goal, w, hl, sph = scene(B, K)
+    prm = params(N)
+    ops, lib = h.ops, h.ops.lib
+    cp, sp = lib.controller_default_params(), lib.simulator_default_params()
+    z = np.zeros((n, 3))
+    st = dict(state=ops.controller_state(cp, n), time=h.to_dev(np.zeros(n)), pos=h.prob(p0[lo:hi]), vel=h.prob(v0[lo:hi]), att=h.prob(z), omega=h.prob(z),
+              U=h.prob(np.tile([0.0, 0.0, prm.mass * prm.gravity], (n, N, 1))), smoother_state=ops.smoother_state(n), mixer_state=ops.mixer_state(n),
+              followed=h.prob(np.zeros((n, 9))), clearance=h.prob(np.full(n, np.inf)) if K else None)
+    fixed = dict(prm=prm, cp=cp, sp=sp, goal=h.prob(goal[lo:hi]), spheres=h.prob(sph) if K else None, wind=h.prob(w[lo:hi]), health=h.prob(hl[lo:hi]),
+                 smoother=SmootherParams.reference_defaults(), mixer=lib.mixer_default_params(), lo=lo, S=S, K=K)
+    return st, fixed
+
+
+def _launch(h, st, fx, cycles, cycle_base=0):
+    return h.ops.mppi_closed_loop_staged(fx["prm"], fx["cp"], fx["sp"], st["state"], st["time"], st["pos"], st["vel"], st["att"], st["omega"], fx["goal"],
+                                         st["U"], cycles, SUBSTEPS, SIM_DT, fx["S"], ITERS, SIGMA, LAM, seed=SEED, cycle_base=cycle_base, shift=1,
+                                         iter_base=5, index_base=fx["lo"], spheres=fx["spheres"], obstacle_weight=W_OBS if fx["K"] else 0.0,
+                                         wind=fx["wind"], want_plan=True, clearance=st["clearance"], smoother=fx["smoother"],
+                                         smoother_state=st["smoother_state"], mixer=fx["mixer"], mixer_state=st["mixer_state"],
+                                         motor_health=fx["health"], followed=st["followed"])
+
+
+def check_continuation(h, shape):
+    """One launch of 4 cycles == launches of 1 + 3 cycles with cycle_base 0 and 1 that carry followed, the records, U and the clearance
+    along: every output and followed as bytes.  Drones [lo, hi) with index_base = lo == those rows of the full batch."""
+    N, B, K, S = shape
+    one, fx = _fresh(h, shape)
+    o1 = _launch(h, one, fx, CYCLES)
+    assert o1["followed"] is one["followed"] and o1["U"] is one["U"]
+    two, _ = _fresh(h, shape)
+    oa = _launch(h, two, fx, 1, 0)
+    ob = _launch(h, two, fx, CYCLES - 1, 1)
+    keys = [k for k in one if one[k] is not None]
+    for k in keys:
+        same_bits(h.to_host(two[k]), h.to_host(one[k]), f"1 + 3 cycles: {k}")
+    same_bits(h.to_host(ob["cost"]), h.to_host(o1["cost"]), "1 + 3 cycles: cost")
+    same_bits(h.to_host(ob["plan_last"]), h.to_host(o1["plan_last"]), "1 + 3 cycles: plan_last")
+    same_bits(np.concatenate([h.to_host(oa["trace"]), h.to_host(ob["trace"])], axis=1), h.to_host(o1["trace"]), "1 + 3 cycles: trace")
+    assert np.abs(h.to_host(one["followed"])).max() > 0, "the launch stores the sample of its last plan"
+    lo, hi = 1, B - 1
+    part, fp = _fresh(h, shape, lo, hi)
+    op = _launch(h, part, fp, CYCLES)
+    for k in keys:
+        same_bits(h.to_host(part[k]), h.to_host(one[k])[lo:hi], f"drones [{lo}, {hi}): {k}")
+    same_bits(h.to_host(op["cost"]), h.to_host(o1["cost"])[lo:hi], "slice: cost")
+    same_bits(h.to_host(op["trace"]), h.to_host(o1["trace"])[lo:hi], "slice: trace")
+
+
+def check_not_vacuous(h, shape):
+    """Conditions on the CHAIN's results (never on the code under test) under which the bit comparisons say something: the stages and the
+    health factors change the flight, the smoother's transition branch runs with the default thresholds and never with the 1e9 ones,
+    nothing blows up."""
+    plain = chain(h, shape, None)
+    runs = {s: chain(h, shape, s) for s in STAGES}
+    runs["no_transition"] = chain(h, shape, "both_health", smoother="no_transition")
+    runs["short_timeout"] = chain(h, shape, "both_health", smoother="short_timeout")
+    for name, r in list(runs.items()) + [("plain", plain)]:
+        for key, v in r.items():
+            assert np.isfinite(v).all(), (name, key)
+        assert not (r["controller_state"][:, 11].astype(np.int64) & 1).any(), f"{name}: a drone ends in the controller's failsafe"
+    for name in ("smoother", "both", "both_health", "both_shared_health", "short_timeout"):
+        assert (runs[name]["smoother_state"][:, 21] > 0).all(), f"{name}: a drone never started a transition"
+    assert (runs["no_transition"]["smoother_state"][:, 21] == 0).all()
+    figures = dict(pos_smoother=np.abs(plain["pos"] - runs["smoother"]["pos"]).max(axis=1).min(),
+                   pos_mixer=np.abs(plain["pos"] - runs["mixer"]["pos"]).max(axis=1).min(),
+                   pos_health=np.abs(runs["both"]["pos"] - runs["both_health"]["pos"]).max(axis=1).min())
+    print(f"{shape} {np.dtype(h.dt).name}: least move of a drone, metres: " + ", ".join(f"{k} {v:.4f}" for k, v in figures.items()))
+    assert all(v > MOVES for v in figures.values()), figures
+
+
+def check_argument_rules(h):
+    import torch
+    ops, lib = h.ops, h.ops.lib
+    suf = "f32" if h.dt == np.float32 else "f64"
+    NULL, SHAPE, PARAM = -1, -3, -4                                             # SE3MPC_ERR_NULL, _SHAPE, _PARAM (include/se3mpc.h)
+    B, N, K = 3, 6, 2
+    prm, cp, sp = params(N), lib.controller_default_params(), lib.simulator_default_params()
+    smp, mp = SmootherParams.reference_defaults(), lib.mixer_default_params()
+    z = lambda *s: h.prob(np.zeros(s))
+    d = lambda *s: h.to_dev(np.zeros(s))
+    time, st, sm, mx = d(B), d(B, 12), d(B, 25), d(B, 5)
+    pos, vel, att, om, goal, health, followed = z(B, 3), z(B, 3), z(B, 3), z(B, 3), z(B, 3), h.prob(np.ones((B, 4))), z(B, 9)
+    U, cost, clr = h.prob(np.tile([0.0, 0.0, prm.mass * prm.gravity], (B, N, 1))), z(B), h.prob(np.full(B, np.inf))
+    sph = h.prob(np.array([[5.0, 5.0, 5.0, 0.5], [-5.0, 5.0, 5.0, 0.5]]))
+    keep = (time, st, sm, mx, pos, vel, att, om, goal, health, followed, U, cost, clr, sph)
+    ptr = ops.be.ptr
+
+    def status(**kw):
+        g = lambda k, default: kw.get(k, default)
+        return lib.loop_status("mppi_closed_loop_staged", suf, g("prm", prm), cp, sp, g("smp", smp), g("mp", mp), g("B", B), g("cycles", 1), g("substeps", 2),
+                               g("sim_dt", 0.01), 0, g("shift", 1), g("S", 64), g("iters", 1), g("sigma", 1.0), g("lam", 1.0), 0, 0, 0, ptr(goal), ptr(sph),
+                               g("K", K), 1.0, None, 0, ptr(time), ptr(pos), ptr(vel), ptr(att), ptr(om), ptr(st), g("sm", ptr(sm)), g("mx", ptr(mx)),
+                               g("health", ptr(health)), g("stride", 4), g("followed", ptr(followed)), g("U", ptr(U)), ptr(cost), None, None, ptr(clr),
+                               ops.be.stream())
+    assert status() == 0
+    assert status(smp=None, sm=0, mp=None, mx=0, health=0, followed=0) == 0      # both stages absent: se3mpc_mppi_closed_loop_*
+    assert status(smp=None, sm=0, followed=0) == 0                               # the mixer alone needs no followed
+    assert status(B=0, followed=0, U=0) == 0 and status(cycles=0, followed=0, U=0) == 0
+    assert status(smp=None) == NULL and status(sm=0) == NULL                    # smoother parameters <-> records
+    assert status(mp=None, health=0) == NULL and status(mx=0) == NULL           # mixer parameters <-> records
+    assert status(mp=None, mx=0) == NULL                                        # motor_health without the mixer
+    assert status(followed=0) == NULL                                           # the smoother needs followed
+    assert status(U=0) == NULL
+    assert status(stride=-1) == SHAPE
+    for field in ("transition_time", "update_dt", "smoothing_window"):
+        broken = SmootherParams.reference_defaults(**{field: float("nan")})
+        assert status(smp=broken) == PARAM, field
+    broken = lib.mixer_default_params(); broken.max_thrust = float("inf")
+    assert status(mp=broken) == PARAM
+    # the rules inherited from se3mpc_mppi_closed_loop_*
+    nan, inf = float("nan"), float("inf")
+    for kw, want in [(dict(S=0), SHAPE), (dict(S=63), SHAPE), (dict(S=96), SHAPE), (dict(S=65536 + 64), SHAPE), (dict(iters=-1), SHAPE), (dict(K=-1), SHAPE),
+                     (dict(K=257), SHAPE), (dict(lam=0.0), PARAM), (dict(lam=nan), PARAM), (dict(lam=inf), PARAM), (dict(sigma=-0.5), PARAM),
+                     (dict(sigma=nan), PARAM), (dict(shift=-1), SHAPE), (dict(shift=N + 1), SHAPE), (dict(B=-1), SHAPE), (dict(cycles=-1), SHAPE),
+                     (dict(substeps=-1), SHAPE), (dict(sim_dt=nan), PARAM), (dict(prm=None), NULL)]:
+        got = status(**kw)
+        assert got == want, f"{kw}: {got} != {want}"
+        assert lib.last_error(), f"{kw}: se3mpc_last_error not set"
+    assert status(shift=0) == 0 and status(shift=N) == 0 and status(substeps=0) == 0
+    if hasattr(torch, "cuda") and torch.cuda.is_available():
+        torch.cuda.synchronize()
+    del keep

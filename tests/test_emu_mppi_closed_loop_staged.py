@@ -1,0 +1,147 @@
+"""CPU suite: se3mpc_mppi_closed_loop_staged_* / Ops.mppi_closed_loop_staged / ClosedLoopMonteCarlo.run_mppi_fused_staged -- the one-launch
+closed-loop MPPI Monte-Carlo with the TrajectorySmoother and the MotorMixer inside -- on the product kernels compiled for the host
+(tests/emu): the checks of tests/mppi_closed_loop_staged_checks.py at the shapes the emulation flies in seconds (EMU_SHAPES there), and the host logic of run_mppi_fused_staged on recorded library calls."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "emu"))
+import build_emu  # noqa: E402
+from numpy_backend import TorchCpuBackend  # noqa: E402
+
+from dart_planner_amd import capi  # noqa: E402
+from dart_planner_amd.ops import Ops  # noqa: E402
+import parity_checks as pc  # noqa: E402
+import mppi_closed_loop_staged_checks as sc  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def emu_ops():
+    return Ops(TorchCpuBackend(), capi.Library(build_emu.build()))
+
+
+def harness(ops, dt):
+    import torch
+    return pc.Harness(ops, lambda a: torch.from_numpy(np.ascontiguousarray(a)).clone(), lambda a: a.numpy(), dt)
+
+
+DTYPES = [np.float64, np.float32]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("shape", sc.EMU_SHAPES)
+def test_chain_conditions_are_not_vacuous(emu_ops, dt, shape):
+    sc.check_not_vacuous(harness(emu_ops, dt), shape)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("shape", sc.EMU_SHAPES)
+@pytest.mark.parametrize("stage", list(sc.STAGES))
+def test_one_launch_equals_the_chain_bit_for_bit(emu_ops, dt, shape, stage):
+    sc.check_equals_chain(harness(emu_ops, dt), shape, stage)
+
+
+def test_a_full_block_equals_the_chain_bit_for_bit(emu_ops):
+    sc.check_equals_chain(harness(emu_ops, np.float32), sc.SHAPES[1], "both_health")
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("shape", sc.EMU_SHAPES)
+@pytest.mark.parametrize("wind", [None, "shared"])
+def test_one_launch_equals_the_chain_without_and_with_shared_wind(emu_ops, dt, shape, wind):
+    sc.check_equals_chain(harness(emu_ops, dt), shape, "both_health", wind=wind)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("shape", sc.EMU_SHAPES)
+@pytest.mark.parametrize("smoother", ["no_transition", "short_timeout"])
+def test_smoother_branches_bit_for_bit(emu_ops, dt, shape, smoother):
+    sc.check_equals_chain(harness(emu_ops, dt), shape, "both_health", smoother=smoother)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("shape", sc.EMU_SHAPES)
+@pytest.mark.parametrize("shift", [0, 1, "N"])
+def test_every_shift_bit_for_bit(emu_ops, dt, shape, shift):
+    sc.check_equals_chain(harness(emu_ops, dt), shape, "both_health", shift=shape[0] if shift == "N" else shift)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_an_act_phase_of_two_chunks_bit_for_bit(emu_ops, dt):
+    sc.check_equals_chain(harness(emu_ops, dt), sc.SHAPES[0], "both_health", substeps=sc.LONG_SUBSTEPS)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("shape", [s for s in sc.EMU_SHAPES if s[2]])
+def test_clearance_agrees_with_the_logged_chain(emu_ops, dt, shape):
+    sc.check_clearance(harness(emu_ops, dt), shape)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("shape", sc.EMU_SHAPES)
+def test_absent_stages_equal_run_mppi_fused(emu_ops, dt, shape):
+    sc.check_without_stages(harness(emu_ops, dt), shape)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("shape", sc.EMU_SHAPES)
+def test_a_second_launch_continues_the_run_and_slices_are_rows(emu_ops, dt, shape):
+    sc.check_continuation(harness(emu_ops, dt), shape)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_argument_rules(emu_ops, dt):
+    sc.check_argument_rules(harness(emu_ops, dt))
+
+
+# ---- host logic of run_mppi_fused_staged: the library calls are recorded, not made, on zero-filled buffers
+def recorded(ops, monkeypatch):
+    import torch
+    calls = []
+    monkeypatch.setattr(ops.lib, "call", lambda base, suf, *args, params=None: calls.append(f"{base}_{suf}"))
+    monkeypatch.setattr(ops.lib, "loop_call", lambda base, suf, *args: calls.append(f"{base}_{suf}"))
+    for name in ("controller_reset", "smoother_reset", "mixer_reset"):
+        monkeypatch.setattr(ops.lib, name, lambda *args, name=name: calls.append(name))
+    monkeypatch.setattr(ops.be, "empty", lambda shape, kind: torch.zeros(shape, dtype=ops.be._dt[kind]))
+    return calls
+
+
+def staged_mc(ops):
+    import torch
+    from dart_planner_amd.capi import Params
+    from dart_planner_amd.control.closed_loop import ClosedLoopMonteCarlo
+    B = 2
+    mc = ClosedLoopMonteCarlo(ops, Params.reference_defaults(horizon=6, dt=0.1))
+    z = lambda *s: torch.zeros(*s, dtype=torch.float64)
+    return mc, (z(B, 3), z(B, 3), torch.ones(B, 3, dtype=torch.float64), 3, 2, 0.01, 64, 2, 1.0, 50.0)
+
+
+@pytest.mark.parametrize("with_smoother,with_mixer", [(False, False), (True, False), (False, True), (True, True)])
+def test_run_mppi_fused_staged_resets_the_stages_present_and_launches_once(emu_ops, monkeypatch, with_smoother, with_mixer):
+    mc, args = staged_mc(emu_ops)                                         # (the default parameters: before the calls are recorded)
+    smoother = capi.SmootherParams.reference_defaults() if with_smoother else None
+    mixer = emu_ops.lib.mixer_default_params() if with_mixer else None
+    calls = recorded(emu_ops, monkeypatch)
+    out = mc.run_mppi_fused_staged(*args, smoother=smoother, mixer=mixer)
+    assert calls == ["controller_reset"] + ["smoother_reset"] * with_smoother + ["mixer_reset"] * with_mixer + ["mppi_closed_loop_staged_f64"]
+    assert ("smoother_state" in out) == with_smoother and ("mixer_state" in out) == with_mixer and ("followed" in out) == with_smoother
+    assert out["clearance"] is None and out["trace"].shape == (2, 3, 2)
+
+
+def test_run_mppi_fused_staged_motor_health_needs_the_mixer(emu_ops):
+    import torch
+    mc, args = staged_mc(emu_ops)
+    with pytest.raises(ValueError, match="mixer"):
+        mc.run_mppi_fused_staged(*args, motor_health=torch.ones(4, dtype=torch.float64))
+    with pytest.raises(ValueError, match="mixer"):
+        mc.run_mppi_fused_staged(*args, smoother=capi.SmootherParams.reference_defaults(), motor_health=torch.ones(4, dtype=torch.float64))
+
+
+def test_run_mppi_fused_still_has_no_stages(emu_ops):
+    mc, args = staged_mc(emu_ops)
+    with pytest.raises(ValueError, match="smoother"):
+        mc.run_mppi_fused(*args, smoother=capi.SmootherParams.reference_defaults())
+    with pytest.raises(ValueError, match="mixer"):
+        mc.run_mppi_fused(*args, mixer=emu_ops.lib.mixer_default_params())

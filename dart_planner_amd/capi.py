@@ -228,9 +228,44 @@ class MixerParams(C.Structure):
 
 assert C.sizeof(MixerParams) == 592       # static_assert of csrc/mixer_device.hpp
 
+
+class OnboardParams(C.Structure):
+    """struct se3mpc_onboard_params == OnboardController.__init__ (src/dart_planner/control/onboard_controller.py:25-35) and the first dt
+    of sense (:139).  pid: rows pos_x, pos_y, pos_z, roll, pitch, yaw_rate; columns Kp, Ki, Kd, integral_limit (0 = no clamp)."""
+    PID_ROWS = ("pos_x", "pos_y", "pos_z", "roll", "pitch", "yaw_rate")
+    _fields_ = [("mass", C.c_double), ("g", C.c_double), ("pid", (C.c_double * 4) * 6), ("first_dt", C.c_double)]
+
+    @classmethod
+    def reference_defaults(cls, **overrides) -> "OnboardParams":
+        """The reference defaults, computed here the way se3mpc_onboard_default_params() does (the test-suite checks the two agree).
+        Overrides: mass, g, first_dt, or a PID row's name = (Kp, Ki, Kd, integral_limit)."""
+        p = cls(mass=1.0, g=9.81, first_dt=0.01)
+        rows = dict(pos_x=(10.0, 1.0, 5.0, 2.0), pos_y=(10.0, 1.0, 5.0, 2.0), pos_z=(12.0, 1.5, 6.0, 2.0), roll=(8.0, 0.0, 2.0, 1.0),
+                    pitch=(8.0, 0.0, 2.0, 1.0), yaw_rate=(4.0, 0.0, 1.0, 0.5))
+        for k, v in overrides.items():
+            if k in rows:
+                rows[k] = tuple(0.0 if x is None else float(x) for x in v)
+            elif k in ("mass", "g", "first_dt"):
+                setattr(p, k, float(v))
+            else:
+                raise AttributeError(f"se3mpc_onboard_params has no field {k!r}")
+        for i, name in enumerate(cls.PID_ROWS):
+            p.pid[i] = (C.c_double * 4)(*rows[name])
+        return p
+
+    def copy(self, **overrides) -> "OnboardParams":
+        rows = {name: tuple(self.pid[i]) for i, name in enumerate(self.PID_ROWS)}
+        return type(self).reference_defaults(**{**dict(mass=self.mass, g=self.g, first_dt=self.first_dt), **rows, **overrides})
+
+
+assert C.sizeof(OnboardParams) == 216     # static_assert of csrc/edge_device.hpp
+
 CONTROLLER_STATE_WORDS = 12
 SMOOTHER_STATE_WORDS = 25
 MIXER_STATE_WORDS = 5
+ONBOARD_STATE_WORDS = 14
+LATENCY_STATE_WORDS = 4
+LATENCY_MAX_DEPTH = 1000
 # flag bits of se3mpc_mixer_mix_* (include/se3mpc.h)
 MIXER_NEGATIVE_THRUST, MIXER_NON_FINITE, MIXER_OVERRUN, MIXER_SATURATION_EVENT, MIXER_ALL_IDLE, MIXER_WATCHDOG = 1, 2, 4, 8, 16, 32
 
@@ -287,6 +322,7 @@ _CP = C.POINTER(ControllerParams)
 _SP = C.POINTER(SimulatorParams)
 _MP = C.POINTER(SmootherParams)
 _XP = C.POINTER(MixerParams)
+_OP = C.POINTER(OnboardParams)
 _LL = C.c_longlong
 _PLAN = [_I, _P, _LL, _P, _LL, _P, _LL, _P, _LL]            # N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA
 # consumer side of the contract: se3mpc_<base>_<suffix>(...)
@@ -308,6 +344,10 @@ _LOOP_TYPED_API = {
     "mixer_readback": [_XP, _I, _P, _P, _LL, _P, _P, _P, _P, _P, _P],
     "closed_loop_actuated": [_MP, _CP, _SP, _XP, _I, _I, _D] + _PLAN + [_P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _LL, _I,
                              C.POINTER(C.c_double * 3), _P, _P, _P, _P, _P, _P, _P],
+    "latency_push": [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "onboard_control": [_OP, _I, _P, _P, _P, _P] + _PLAN + [_P, _P, _P, _P, _P],
+    "edge_loop": [_OP, _SP, _I, _I, _D] + _PLAN + [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _LL, _I, C.POINTER(C.c_double * 3),
+                  _P, _P, _P, _P, _P, _P, _P],
     "monte_carlo": [_PP, _CP, _SP, _I, _I, _I, _D, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "monte_carlo_staged": [_PP, _CP, _SP, _MP, _XP, _I, _I, _I, _D, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P],
     "mppi_closed_loop": [_PP, _CP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _D, _P, _LL,
@@ -323,6 +363,9 @@ _PLAIN_API = {
     "se3mpc_smoother_reset": (C.c_int, [_I, _P, _P]),
     "se3mpc_mixer_default_params": (C.c_int, [_XP]),
     "se3mpc_mixer_reset": (C.c_int, [_I, _P, _P]),
+    "se3mpc_onboard_default_params": (C.c_int, [_OP]),
+    "se3mpc_onboard_reset": (C.c_int, [_I, _P, _P]),
+    "se3mpc_latency_reset": (C.c_int, [_I, _I, _P, _P]),
     "se3mpc_abi_version": (C.c_int, []),
     "se3mpc_last_error": (C.c_char_p, []),
     "se3mpc_device_count": (C.c_int, []),
@@ -330,6 +373,7 @@ _PLAIN_API = {
     "se3mpc_check_params": (C.c_int, [_PP]),
     "se3mpc_set_rollout_variant": (C.c_int, [_I]),
     "se3mpc_set_solver_variant": (C.c_int, [_I]),
+    "se3mpc_set_edge_loop_variant": (C.c_int, [_I]),
     "se3mpc_reduce_keys": (C.c_int, [_P, _I, _I, _P, _P]),
     "se3mpc_key_index": (C.c_uint32, [C.c_uint64]),
     "se3mpc_key_cost": (C.c_float, [C.c_uint64]),
@@ -416,6 +460,9 @@ class Library:
     def set_solver_variant(self, variant: int) -> None:
         self._check("se3mpc_set_solver_variant", self._dll.se3mpc_set_solver_variant(variant))
 
+    def set_edge_loop_variant(self, variant: int) -> None:
+        self._check("se3mpc_set_edge_loop_variant", self._dll.se3mpc_set_edge_loop_variant(variant))
+
     def reduce_keys(self, wave_keys: int, per_batch: int, nbatch: int, keys_out: int, stream: int) -> None:
         self._check("se3mpc_reduce_keys", self._dll.se3mpc_reduce_keys(wave_keys, per_batch, nbatch, keys_out, stream))
 
@@ -481,6 +528,17 @@ class Library:
     def mixer_reset(self, B: int, state: int, stream: int) -> None:
         self._check("se3mpc_mixer_reset", self._dll.se3mpc_mixer_reset(B, state, stream))
 
+    def onboard_default_params(self) -> OnboardParams:
+        p = OnboardParams()
+        self._check("se3mpc_onboard_default_params", self._dll.se3mpc_onboard_default_params(C.byref(p)))
+        return p
+
+    def onboard_reset(self, B: int, state: int, stream: int) -> None:
+        self._check("se3mpc_onboard_reset", self._dll.se3mpc_onboard_reset(B, state, stream))
+
+    def latency_reset(self, B: int, depth: int, state: int, stream: int) -> None:
+        self._check("se3mpc_latency_reset", self._dll.se3mpc_latency_reset(B, depth, state, stream))
+
     def loop_call(self, base: str, suffix: str, *args) -> None:
         """se3mpc_control_<suffix> / se3mpc_closed_loop_<suffix>; struct arguments are passed by reference here."""
         a = [C.byref(x) if isinstance(x, _STRUCTS) else x for x in args]
@@ -509,7 +567,7 @@ class Library:
             raise Se3mpcError(name, rc, self.last_error() if rc == -6 else "")
 
 
-_STRUCTS = (ControllerParams, SimulatorParams, SmootherParams, MixerParams, Params)
+_STRUCTS = (ControllerParams, SimulatorParams, SmootherParams, MixerParams, OnboardParams, Params)
 _default: Optional[Library] = None
 
 

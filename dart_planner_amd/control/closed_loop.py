@@ -13,12 +13,14 @@ smoother) puts the reference's MotorMixer and motor model behind the controller:
 simulator flies under what the motors deliver, ``motor_health`` scaling each motor's thrust.  ``run_fused_staged`` flies both
 stages inside the one-launch solver-based Monte-Carlo (``se3mpc_monte_carlo_staged_*``), ``run_mppi_fused_staged`` inside the
 one-launch MPPI Monte-Carlo, where the clearance to the spheres is measured too (``se3mpc_mppi_closed_loop_staged_*``, DESIGN.md 5.8d);
-``run_fused``, ``run_mppi_fused`` and ``capture`` do not have them.
+``run_fused``, ``run_mppi_fused`` and ``capture`` do not have them.  ``run_edge`` flies the reference's OTHER edge loop (edge/main.py:21-112) under the
+same planner: a latency buffer between the drone's state and its controller, and the cascaded-PID OnboardController in place of the geometric one
+(``se3mpc_edge_loop_*``).
 """
 import math
 from typing import Optional
 
-from ..capi import ControllerParams, MixerParams, Params, SimulatorParams, SmootherParams
+from ..capi import ControllerParams, MixerParams, OnboardParams, Params, SimulatorParams, SmootherParams
 
 
 class ClosedLoopMonteCarlo:
@@ -122,6 +124,35 @@ class ClosedLoopMonteCarlo:
             if log:
                 logs.append((sol, out))
         return self._result(st, sm, fl, logs=logs, mixer_state=mx)
+
+    def run_edge(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, latency_depth: int = 5, onboard: Optional[OnboardParams] = None,
+                 wind=None, log: bool = False):
+        """The receding-horizon Monte-Carlo on the reference's edge loop (edge/main.py:80-95): per cycle one solve launch, as :meth:`run`,
+        then ONE ``se3mpc_edge_loop_*`` launch of `substeps` x (latency push -> OnboardController.compute_control_command -> DroneSimulator.step)
+        that reads the plan in place.  latency_depth: slots of the estimator -> controller buffer (5 = hardware.yaml's 25 ms at 5 ms; 0 = no
+        buffer); onboard: the controller's parameters (None: OnboardController()).  The first popped state is older than the controller's
+        clock, so with a buffer every drone gets one zero command (thrust 0, torque 0) at step `latency_depth` of the first cycle.
+        -> dict(pos, vel, att, omega (B, 3), time (B,), onboard_state (B, 14), latency = the buffer (Ops.latency_buffer), zero_thrust_steps
+        int32 (B,) = the steps whose commanded thrust was exactly 0, logs = [(solve outputs, edge-loop outputs)] if log)."""
+        import torch
+        ops, prm = self.ops, self.params
+        B, N = p0.shape[0], prm.horizon
+        op = onboard if onboard is not None else ops.lib.onboard_default_params()
+        _, _, fl = self._start(p0, v0)
+        st = ops.onboard_state(B)
+        buf = ops.latency_buffer(B, latency_depth, ops.be.suffix(p0))
+        zeros = torch.zeros(B, dtype=torch.int32, device=ops.be.device)
+        k = torch.arange(N, dtype=torch.float64, device=ops.be.device)
+        logs, sol = [], None
+        for c in range(cycles):
+            sol = ops.solve(prm, fl[1], fl[2], goal, want_trajectory=True if log else "accelerations", out=None if log else sol)
+            X = sol["x"]
+            out = ops.edge_loop(op, self.simulator, st, buf, *fl, (c * substeps * sim_dt) + k * prm.dt, X, X[:, 3 * N:], sol["accelerations"], nsteps=substeps,
+                                sim_dt=sim_dt, strides=(9 * N, 9 * N, 3 * N), wind=wind, log=log, zero_thrust_steps=zeros)
+            if log:
+                logs.append((sol, out))
+        time, pos, vel, att, om = fl
+        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, onboard_state=st, latency=buf, zero_thrust_steps=zeros, logs=logs)
 
     def run_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, wind=None, want_last_plan: bool = False, smoother=None,
                   mixer=None, motor_health=None):

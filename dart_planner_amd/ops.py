@@ -17,8 +17,9 @@ import ctypes as _C
 
 import numpy as np
 
-from .capi import (CONTROLLER_STATE_WORDS, MIXER_STATE_WORDS, SMOOTHER_STATE_WORDS, ControllerParams, MixerParams, Library, Params, SimulatorParams, SmootherParams, SolveInfo,
-                   get_library, SE3MPC_MAX_SPHERES)
+from .capi import (CONTROLLER_STATE_WORDS, LATENCY_MAX_DEPTH, LATENCY_STATE_WORDS, MIXER_STATE_WORDS, ONBOARD_STATE_WORDS, SMOOTHER_STATE_WORDS,
+                   SE3MPC_MAX_SPHERES, ControllerParams, Library, MixerParams, OnboardParams, Params, SimulatorParams, SmootherParams, SolveInfo,
+                   get_library)
 
 INFO_DTYPE = np.dtype([("fun", "<f8"), ("nit", "<i4"), ("nfev", "<i4"), ("status", "<i4"), ("task", "<i4")])
 assert INFO_DTYPE.itemsize == 24
@@ -989,6 +990,117 @@ class Ops:
                            self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega), self.be.ptr(state), self.be.ptr(smoother_state),
                            self.be.ptr(wind), w_stride, gust_step, gust_vec, self.be.ptr(logs.get("log_state")), self.be.ptr(logs.get("log_cmd")),
                            self.be.ptr(logs.get("log_time")), self.be.ptr(logs.get("log_target")), self.be.stream())
+        return logs
+
+    # ------------------------------------------------------------------ latency buffer and OnboardController (per-drone rows)
+    def onboard_state(self, B: int):
+        """Fresh OnboardController members for B drones (reset()): float64 (B, 14), all zero = last_time None."""
+        st = self.be.empty((B, ONBOARD_STATE_WORDS), "f64")
+        self.lib.onboard_reset(B, self.be.ptr(st), self.be.stream())
+        return st
+
+    def latency_buffer(self, B: int, depth: int, suf: str):
+        """An empty DroneStateLatencyBuffer of `depth` slots for B drones -> dict(depth, ring (depth, 12, B) of the precision `suf`, ring_time
+        float64 (depth, B), state float64 (B, 4)); depth = 0 -> dict(depth=0, ring=None, ring_time=None, state=None): no buffer.  The
+        ring is zero-filled here only so that a copy of it is reproducible; no slot is read before it is written."""
+        depth = int(depth)
+        if depth == 0:
+            return dict(depth=0, ring=None, ring_time=None, state=None)
+        if not 1 <= depth <= LATENCY_MAX_DEPTH:
+            raise ValueError(f"latency depth: 0 (no buffer) or 1..{LATENCY_MAX_DEPTH}")
+        ring, ring_time = self.be.empty((depth, 12, B), suf), self.be.empty((depth, B), "f64")
+        ring[...] = 0; ring_time[...] = 0
+        st = self.be.empty((B, LATENCY_STATE_WORDS), "f64")
+        self.lib.latency_reset(B, depth, self.be.ptr(st), self.be.stream())
+        return dict(depth=depth, ring=ring, ring_time=ring_time, state=st)
+
+    def _latency(self, buf, B, suf):
+        """A latency_buffer() dict checked against the call -> (depth, ring, ring_time, state) pointers."""
+        depth = int(buf["depth"])
+        if depth == 0:
+            return 0, 0, 0, 0
+        if not 1 <= depth <= LATENCY_MAX_DEPTH:
+            raise ValueError(f"latency depth: 0 (no buffer) or 1..{LATENCY_MAX_DEPTH}")
+        ring, rt, st = buf["ring"], buf["ring_time"], buf["state"]
+        for a, nm in ((ring, "ring"), (rt, "ring_time"), (st, "latency state")):
+            self.be.check(a, nm)
+        if tuple(ring.shape) != (depth, 12, B) or self.be.suffix(ring) != suf:
+            raise ValueError(f"ring: ({depth}, 12, {B}) {suf}, got {tuple(ring.shape)}")
+        if tuple(rt.shape) != (depth, B) or self.be.suffix(rt) != "f64":
+            raise ValueError(f"ring_time: float64 ({depth}, {B})")
+        if tuple(st.shape) != (B, LATENCY_STATE_WORDS) or self.be.suffix(st) != "f64":
+            raise ValueError(f"latency state: float64 ({B}, {LATENCY_STATE_WORDS})")
+        return depth, self.be.ptr(ring), self.be.ptr(rt), self.be.ptr(st)
+
+    def _onboard_record(self, state, B):
+        self.be.check(state, "onboard state")
+        if tuple(state.shape) != (B, ONBOARD_STATE_WORDS) or self.be.suffix(state) != "f64":
+            raise ValueError(f"onboard state: float64 ({B}, {ONBOARD_STATE_WORDS})")
+
+    def latency_push(self, buf, time, pos, vel, att, omega):
+        """DroneStateLatencyBuffer.push(state, state.timestamp) for B drones on a latency_buffer() (depth >= 1), updated in place.
+        -> dict(time float64 (B,), pos, vel, att, omega (B, 3)): the delayed state (the current one while the buffer fills)."""
+        B = time.shape[0]
+        suf = self.be.suffix(pos)
+        self._drone_state(B, suf, pos, vel, att, omega)
+        self._clock(time, B, "time")
+        if int(buf["depth"]) < 1:
+            raise ValueError("latency_push needs a buffer of depth >= 1")
+        depth, ring, rt, st = self._latency(buf, B, suf)
+        out = dict(time=self.be.empty((B,), "f64"), pos=self.be.empty((B, 3), suf), vel=self.be.empty((B, 3), suf), att=self.be.empty((B, 3), suf),
+                   omega=self.be.empty((B, 3), suf))
+        self.lib.loop_call("latency_push", suf, B, depth, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega),
+                           ring, rt, st, self.be.ptr(out["time"]), self.be.ptr(out["pos"]), self.be.ptr(out["vel"]), self.be.ptr(out["att"]),
+                           self.be.ptr(out["omega"]), self.be.stream())
+        return out
+
+    _NO_PLAN = [0, 0, 0, 0, 0, 0, 0, 0, 0]          # the nine plan arguments of "no plan": N = 0 rows, NULL pointers
+
+    def onboard_control(self, op: OnboardParams, state, time, pos, att, omega, timestamps=None, P=None, V=None, A=None, strides=None):
+        """OnboardController.compute_control_command for B drones: time float64 (B,) = state.timestamp, pos, att, omega (B, 3); the plan as in
+        :meth:`closed_loop`, or timestamps = None: no plan -> get_fallback_command with target = pos and `state` untouched.  `state`
+        float64 (B, 14) is updated in place.  -> dict(thrust (B,), torque (B, 3), target_pos (B, 3))."""
+        B = time.shape[0]
+        suf = self.be.suffix(pos)
+        self._drone_state(B, suf, pos, None, att, omega)
+        self._clock(time, B, "time")
+        self._onboard_record(state, B)
+        plan = self._NO_PLAN if timestamps is None else self._plan_ptrs(B, suf, timestamps, P, V, A, strides)
+        out = dict(thrust=self.be.empty((B,), suf), torque=self.be.empty((B, 3), suf), target_pos=self.be.empty((B, 3), suf))
+        self.lib.loop_call("onboard_control", suf, op, B, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(att), self.be.ptr(omega), *plan,
+                           self.be.ptr(state), self.be.ptr(out["thrust"]), self.be.ptr(out["torque"]), self.be.ptr(out["target_pos"]), self.be.stream())
+        return out
+
+    def edge_loop(self, op: OnboardParams, sp: SimulatorParams, onboard_state, buf, time, pos, vel, att, omega, timestamps=None, P=None, V=None,
+                  A=None, nsteps: int = 1, sim_dt: float = 0.01, strides=None, wind=None, gust=None, log: bool = False, zero_thrust_steps=None):
+        """`nsteps` x (latency push -> compute_control_command or fallback -> DroneSimulator.step) for B drones in ONE launch: the body of the
+        reference's edge loop (edge/main.py:80-95).  buf: a latency_buffer() (depth 0 = none); the plan as in :meth:`closed_loop`, or
+        timestamps = None: no plan (the fallback command).  time, pos, vel, att, omega, `onboard_state` (B, 14) and the buffer are updated in
+        place; zero_thrust_steps: None or int32 (B,) counters that are incremented.
+        -> dict([log_state (nsteps, B, 12), log_cmd (nsteps, B, 4), log_time (nsteps, B), log_target (nsteps, B, 3), log_delayed_time
+        (nsteps, B)])."""
+        B = time.shape[0]
+        suf = self.be.suffix(pos)
+        self._drone_state(B, suf, pos, vel, att, omega)
+        self._clock(time, B, "time")
+        self._onboard_record(onboard_state, B)
+        depth, ring, rt, lst = self._latency(buf, B, suf)
+        plan = self._NO_PLAN if timestamps is None else self._plan_ptrs(B, suf, timestamps, P, V, A, strides)
+        w_stride = self._wind(wind, B, suf)
+        gust_step, gust_vec = self._gust(gust)
+        nsteps = int(nsteps)
+        logs = self._loop_logs(nsteps, B, suf, log)
+        if log:
+            logs.update(log_target=self.be.empty((nsteps, B, 3), suf), log_delayed_time=self.be.empty((nsteps, B), "f64"))
+        if zero_thrust_steps is not None:
+            self.be.check(zero_thrust_steps, "zero_thrust_steps")
+            if tuple(zero_thrust_steps.shape) != (B,) or zero_thrust_steps.dtype != self.be.empty((0,), "i32").dtype:
+                raise ValueError(f"zero_thrust_steps: int32 ({B},)")
+        self.lib.loop_call("edge_loop", suf, op, sp, B, nsteps, float(sim_dt), *plan, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel),
+                           self.be.ptr(att), self.be.ptr(omega), self.be.ptr(onboard_state), depth, ring, rt, lst, self.be.ptr(wind), w_stride,
+                           gust_step, gust_vec, self.be.ptr(logs.get("log_state")), self.be.ptr(logs.get("log_cmd")), self.be.ptr(logs.get("log_time")),
+                           self.be.ptr(logs.get("log_target")), self.be.ptr(logs.get("log_delayed_time")), self.be.ptr(zero_thrust_steps),
+                           self.be.stream())
         return logs
 
     # ------------------------------------------------------------------ MotorMixer and motor model (per-drone rows)

@@ -917,6 +917,97 @@ int se3mpc_mppi_closed_loop_staged_f64(const se3mpc_params* p, const se3mpc_cont
                                        const double* motor_health, long long health_stride, double* followed, double* U, double* cost,
                                        double* trace, double* plan_last, double* clearance, void* stream);
 
+/* ------------------------------------------------------------------ latency buffer and OnboardController
+ * The reference's edge loop (edge/main.py:21-112; "latency.py" = src/dart_planner/utils/latency_buffer.py, "pid.py" =
+ * src/dart_planner/utils/pid_controller.py, "onboard.py" = src/dart_planner/control/onboard_controller.py), one drone per lane, reproduced
+ * with its quirks: while the buffer fills, push returns the CURRENT state (latency.py:68-73), so the first delayed state the controller
+ * sees carries a timestamp that is not later than its last_time and compute_control_command answers thrust 0, torque 0, target (0, 0, 0)
+ * for that one step (onboard.py:176-177, with last_time already moved by sense, :139-140).  All clock arithmetic is double. */
+
+/* OnboardController.__init__ (onboard.py:25-35) and the first dt of sense (:139). */
+typedef struct se3mpc_onboard_params {
+  double mass, g;                              /* mass > 0                                                  (onboard.py:25-27) */
+  double pid[6][4];                            /* rows pos_x, pos_y, pos_z, roll, pitch, yaw_rate; columns Kp, Ki, Kd, integral_limit
+                                                  (0 = no clamp: `if self.integral_limit:`, pid.py:37)     (onboard.py:30-35) */
+  double first_dt;                             /* dt of the first call, when last_time is None              (onboard.py:139)   */
+} se3mpc_onboard_params;
+
+/* Mutable OnboardController members, SE3MPC_ONBOARD_STATE_WORDS doubles per drone: [0..5] integral of pos_x, pos_y, pos_z, roll, pitch,
+ * yaw_rate; [6..11] last_error, same order; [12] last_time; [13] 1 if last_time is not None.  (The setpoints are overwritten on every
+ * call and are not state.) */
+#define SE3MPC_ONBOARD_STATE_WORDS 14
+/* LatencyBuffer members (latency.py:45-52), SE3MPC_LATENCY_STATE_WORDS doubles per drone: [0] len(buffer); [1] the ring slot of the oldest
+ * entry; [2] total_samples; [3] actual_delay_s.  missed_samples = min(total_samples, depth), fill_percentage and is_ready follow. */
+#define SE3MPC_LATENCY_STATE_WORDS 4
+/* The reference's max_buffer_size (latency.py:34). */
+#define SE3MPC_LATENCY_MAX_DEPTH 1000
+
+int se3mpc_onboard_default_params(se3mpc_onboard_params* out);
+/* LatencyBuffer.reset (latency.py:104-111) for B drones of a buffer of `depth` slots: state = device double[B][4], all zero.  The ring
+ * itself needs no clearing: a slot is written before it is read. */
+int se3mpc_latency_reset(int B, int depth, double* state, void* stream);
+/* OnboardController.reset (onboard.py:186-193) for B drones: state = device double[B][14], all zero (last_time None). */
+int se3mpc_onboard_reset(int B, double* state, void* stream);
+
+/* DroneStateLatencyBuffer.push(state, state.timestamp) (latency.py:54-82) for B drones: time [B], pos, vel, att, omega [B][3] in; the
+ * delayed state d_time [B], d_pos, d_vel, d_att, d_omega [B][3] out (the current state while the buffer fills, :68-73).  The buffer is
+ * the caller's: ring [depth][12][B] (pos, vel, att, omega; field-major, drone innermost), ring_time double [depth][B], state [B][4];
+ * all three in / out.  1 <= depth <= SE3MPC_LATENCY_MAX_DEPTH.  A record whose length or slot lies outside the ring reads as empty.
+ * Argument rules of the entry points of this section: a NULL required operand: SE3MPC_ERR_NULL; B < 0, nsteps < 0, a negative stride,
+ * a plan of more than 4096 rows, depth outside its range: SE3MPC_ERR_SHAPE; non-finite gains, limits, g, first_dt or sim_dt, mass not
+ * positive: SE3MPC_ERR_PARAM.  B = 0 and nsteps = 0 are no-ops.  Every rejected call sets se3mpc_last_error and launches nothing. */
+int se3mpc_latency_push_f32(int B, int depth, const double* time, const float* pos, const float* vel, const float* att,
+                            const float* omega, float* ring, double* ring_time, double* state, double* d_time, float* d_pos, float* d_vel,
+                            float* d_att, float* d_omega, void* stream);
+int se3mpc_latency_push_f64(int B, int depth, const double* time, const double* pos, const double* vel, const double* att,
+                            const double* omega, double* ring, double* ring_time, double* state, double* d_time, double* d_pos,
+                            double* d_vel, double* d_att, double* d_omega, void* stream);
+
+/* OnboardController.compute_control_command(state, trajectory) (onboard.py:172-180: sense :136-142, plan :144-161, act :163-170, the six
+ * PIDController.update calls pid.py:25-51 term by term) for B drones: time [B] = state.timestamp, pos, att, omega [B][3] (the velocity is
+ * not read by the control law), plans as in se3mpc_closed_loop_* (N >= 0 rows).  Outputs (any may be NULL): thrust [B], torque [B][3],
+ * target_pos [B][3].  dt <= 0 gives thrust 0, torque 0, target (0, 0, 0) with last_time moved and the PIDs untouched (:176-177).
+ * N = 0 (no plan) gives get_fallback_command (:182-184): thrust mass * g, torque 0, target = pos, and the record is untouched
+ * (edge/main.py:91-94).  `state` [B][14] is read and updated. */
+int se3mpc_onboard_control_f32(const se3mpc_onboard_params* op, int B, const double* time, const float* pos, const float* att,
+                               const float* omega, int N, const double* timestamps, long long ts_stride, const float* P, long long strideP,
+                               const float* V, long long strideV, const float* A, long long strideA, double* state, float* thrust,
+                               float* torque, float* target_pos, void* stream);
+int se3mpc_onboard_control_f64(const se3mpc_onboard_params* op, int B, const double* time, const double* pos, const double* att,
+                               const double* omega, int N, const double* timestamps, long long ts_stride, const double* P,
+                               long long strideP, const double* V, long long strideV, const double* A, long long strideA, double* state,
+                               double* thrust, double* torque, double* target_pos, void* stream);
+
+/* The body of the reference's edge loop (edge/main.py:80-95), `nsteps` times per drone in ONE launch:  delayed = latency_buffer.push(state)
+ * [depth = 0: no buffer, delayed = state];  cmd, target = compute_control_command(delayed, plan) [N = 0: get_fallback_command, target =
+ * delayed.position];  [step == gust_step: the wind becomes gust_wind];  state = DroneSimulator.step(state, cmd, sim_dt).  Arguments as
+ * se3mpc_closed_loop_* (no stop_at_plan_end: every drone takes nsteps), plus the onboard parameters and records onboard_state [B][14],
+ * the buffer (depth, ring, ring_time, latency_state as se3mpc_latency_push_*; with depth = 0 the three may be NULL) and the logs
+ * log_target [nsteps][B][3], log_delayed_time double [nsteps][B] (each NULL or kept) next to log_state / log_cmd / log_time of
+ * se3mpc_closed_loop_*; zero_thrust_steps: NULL, or int32 [B] counters (in / out) of the steps whose commanded thrust was exactly 0.
+ * The same bits as nsteps chained se3mpc_latency_push_* -> se3mpc_onboard_control_* -> se3mpc_simulator_step_* launches. */
+int se3mpc_edge_loop_f32(const se3mpc_onboard_params* op, const se3mpc_simulator_params* sp, int B, int nsteps, double sim_dt, int N,
+                         const double* timestamps, long long ts_stride, const float* P, long long strideP, const float* V,
+                         long long strideV, const float* A, long long strideA, double* time, float* pos, float* vel, float* att,
+                         float* omega, double* onboard_state, int depth, float* ring, double* ring_time, double* latency_state,
+                         const float* wind, long long wind_stride, int gust_step, const double* gust_wind, float* log_state,
+                         float* log_cmd, double* log_time, float* log_target, double* log_delayed_time, int32_t* zero_thrust_steps,
+                         void* stream);
+int se3mpc_edge_loop_f64(const se3mpc_onboard_params* op, const se3mpc_simulator_params* sp, int B, int nsteps, double sim_dt, int N,
+                         const double* timestamps, long long ts_stride, const double* P, long long strideP, const double* V,
+                         long long strideV, const double* A, long long strideA, double* time, double* pos, double* vel, double* att,
+                         double* omega, double* onboard_state, int depth, double* ring, double* ring_time, double* latency_state,
+                         const double* wind, long long wind_stride, int gust_step, const double* gust_wind, double* log_state,
+                         double* log_cmd, double* log_time, double* log_target, double* log_delayed_time, int32_t* zero_thrust_steps,
+                         void* stream);
+
+/* MEASUREMENT KNOB, not part of the interface a caller should build on (as se3mpc_set_rollout_variant): when se3mpc_edge_loop_* loads the ring
+ * entry a push pops.  0 (default): one step ahead, before the previous step's controller and simulator arithmetic (depth >= 2; DESIGN.md
+ * 5.7f).  1: in the push that pops it.  Same bits either way; 1 exists only so that tools/gpu_probe_edge_loop.py can time the difference.
+ * The setting is one process-wide word read at launch time: it is not per stream or per thread, so leave it alone outside a measurement.
+ * Any other value: SE3MPC_ERR_PARAM. */
+int se3mpc_set_edge_loop_variant(int variant);
+
 /* ------------------------------------------------------------------ problem layout: [b][row]
  * The batched solve: replaces _solve_se3_mpc (planner.py:230-280) = cold start (or a caller
  * x0), box, scipy.optimize.minimize(method="L-BFGS-B", jac=..., bounds=..., maxiter, gtol,

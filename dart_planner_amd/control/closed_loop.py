@@ -15,7 +15,7 @@ stages inside the one-launch solver-based Monte-Carlo (``se3mpc_monte_carlo_stag
 one-launch MPPI Monte-Carlo, where the clearance to the spheres is measured too (``se3mpc_mppi_closed_loop_staged_*``, DESIGN.md 5.8d);
 ``run_fused``, ``run_mppi_fused`` and ``capture`` do not have them.  ``run_edge`` flies the reference's OTHER edge loop (edge/main.py:21-112) under the
 same planner: a latency buffer between the drone's state and its controller, and the cascaded-PID OnboardController in place of the geometric one
-(``se3mpc_edge_loop_*``).
+(``se3mpc_edge_loop_*``); ``run_edge_fused`` flies it inside one launch (``se3mpc_monte_carlo_edge_*``).
 """
 import math
 from typing import Optional
@@ -133,7 +133,8 @@ class ClosedLoopMonteCarlo:
         buffer); onboard: the controller's parameters (None: OnboardController()).  The first popped state is older than the controller's
         clock, so with a buffer every drone gets one zero command (thrust 0, torque 0) at step `latency_depth` of the first cycle.
         -> dict(pos, vel, att, omega (B, 3), time (B,), onboard_state (B, 14), latency = the buffer (Ops.latency_buffer), zero_thrust_steps
-        int32 (B,) = the steps whose commanded thrust was exactly 0, logs = [(solve outputs, edge-loop outputs)] if log)."""
+        int32 (B,) = the steps whose commanded thrust was exactly 0, logs = [(solve outputs, edge-loop outputs)] if log).
+        :meth:`run_edge_fused` is the same run in one launch (``se3mpc_monte_carlo_edge_*``; measured at 0.74 - 0.79 of this chain's time for 4096 drones, 0.87 for 64: DESIGN.md 5.7g)."""
         import torch
         ops, prm = self.ops, self.params
         B, N = p0.shape[0], prm.horizon
@@ -153,6 +154,37 @@ class ClosedLoopMonteCarlo:
                 logs.append((sol, out))
         time, pos, vel, att, om = fl
         return dict(pos=pos, vel=vel, att=att, omega=om, time=time, onboard_state=st, latency=buf, zero_thrust_steps=zeros, logs=logs)
+
+    def run_edge_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, latency_depth: int = 5,
+                       onboard: Optional[OnboardParams] = None, wind=None, want_last_plan: bool = False):
+        """:meth:`run_edge` in ONE launch (``se3mpc_monte_carlo_edge_*``): every cycle's solve and its `substeps` x (latency push ->
+        OnboardController -> DroneSimulator.step) inside one kernel, where :meth:`run_edge` makes two launches per cycle.  Same code, same bits
+        and the same result keys as :meth:`run_edge` (no logs), plus last_plan as :meth:`run_fused`.  All cross-cycle state is in the returned
+        operands (onboard_state, latency, time), so ``Ops.monte_carlo_edge`` with ``first_cycle=cycles`` continues the run.  If a solve needed
+        more L-BFGS memory than the launch's LDS image holds (never with the reference's options) the run is repeated by :meth:`run_edge`.
+
+        Measured on an MI355X (``profiles/monte_carlo_edge.json``; 4096 drones, 33 cycles x 15 steps, horizon 6): 1.49 ms
+        (float32) / 1.58 ms (float64) without a buffer and 1.76 / 1.93 ms at depth 5, against 1.97 / 2.13 and 2.24 / 2.49 ms for the 66 launches of
+        :meth:`run_edge` -- 0.74 - 0.79 of the chain's time; at 64 drones, depth 5, 1.73 / 1.87 against 1.97 / 2.15 ms (0.87 - 0.88).  The launch is bound
+        by one drone's dependent chain (64 drones take as long as 4096), the chain by its launches and by the wait for the slowest solve.  Use this form
+        at both batch sizes; beyond 8192 drones at horizon 6 the launch's wavefronts no longer all run at once and neither form is measured there;
+        :meth:`run_edge` stays the form with per-step logs."""
+        import torch
+        ops = self.ops
+        B = p0.shape[0]
+        op = onboard if onboard is not None else ops.lib.onboard_default_params()
+        # the flight state of _start, without the geometric controller's records: this loop has none
+        fl = (torch.zeros(B, dtype=torch.float64, device=ops.be.device), p0.clone(), v0.clone(), torch.zeros_like(p0), torch.zeros_like(p0))
+        st = ops.onboard_state(B)
+        buf = ops.latency_buffer(B, latency_depth, ops.be.suffix(p0))
+        zeros = torch.zeros(B, dtype=torch.int32, device=ops.be.device)
+        out = ops.monte_carlo_edge(self.params, op, self.simulator, st, buf, *fl, goal, cycles, substeps, sim_dt, wind=wind, zero_thrust_steps=zeros,
+                                   want_last_plan=want_last_plan)
+        if int(ops.be.to_host(out["overflowed"])[0]) != 0:
+            return self.run_edge(p0, v0, goal, cycles, substeps, sim_dt, latency_depth=latency_depth, onboard=onboard, wind=wind)
+        time, pos, vel, att, om = fl
+        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, onboard_state=st, latency=buf, zero_thrust_steps=zeros, logs=[],
+                    last_plan=out if want_last_plan else None)
 
     def run_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, wind=None, want_last_plan: bool = False, smoother=None,
                   mixer=None, motor_health=None):

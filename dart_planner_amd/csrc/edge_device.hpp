@@ -190,6 +190,26 @@ struct LatencyLane {
   }
 };
 
+// One step of the reference's edge loop (edge/main.py:81-95) for one drone: the push through its buffer (depth = 0: none, delayed = the
+// state), the OnboardController on the delayed state against the N-row plan (N = 0: the fallback), the count of a commanded thrust of
+// exactly 0, the simulator step under the command.  -> the command (th, tq); log(target [3], delayed clock) is called between command and
+// simulator step.  The step of se3mpc_edge_loop_* (through lane_loop) and of se3mpc_monte_carlo_edge_*: one definition,
+// hence the same bits.
+template <typename R, typename F>
+__device__ __forceinline__ void edge_step(const OnboardDev<R>& c, const SimDev<R>& m, OnboardRegs<R>& s, PlanCursor<R>& cur, LatencyLane<R>& lat,
+                                          int depth, bool early, int N, const double* ts, const R* P, const R* V, const R* A, DroneRegs<R>& d,
+                                          R dt, double sim_dt, int& zeros, R& th, R tq[3], F&& log) {
+  DroneRegs<R> del;
+  if (depth > 0) lat.push(d, del, early);                                         // edge/main.py:81-85
+  else del = d;
+  R tg[3];
+  if (N > 0) onboard_step<R>(c, s, cur, N, ts, P, V, A, del.t, del.p, del.a, del.w, th, tq, tg);   // :87-90
+  else onboard_fallback<R>(c, del.p, th, tq, tg);                                 // :91-94
+  log(tg, del.t);
+  if (th == (R)0) ++zeros;
+  simulator_step<R>(m, d.p, d.v, d.a, d.w, d.t, th, tq, dt, sim_dt, d.wd);        // :95
+}
+
 static inline int check_onboard_params(const se3mpc_onboard_params* p) {
   if (p == nullptr) return SE3MPC_ERR_NULL;
   const double* d = reinterpret_cast<const double*>(p);

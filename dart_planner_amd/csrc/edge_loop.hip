@@ -97,16 +97,11 @@ edge_loop_kernel(OnboardDev<R> c, SimDev<R> m, int B, int nsteps, double sim_dt,
   if (depth > 0) lat.begin(latency_state + (size_t)b * SE3MPC_LATENCY_STATE_WORDS);
   int zeros = 0;
   lane_loop<R>(d, b, B, nsteps, gust_step, gx, gy, gz, false, 0.0, log_state, log_cmd, log_time, [&](int step, R& th, R* tq) {
-    DroneRegs<R> del;
-    if (depth > 0) lat.push(d, del, early_load != 0 && step + 1 < nsteps);                            // edge/main.py:81-85
-    else del = d;
-    R tg[3];
-    if (N > 0) onboard_step<R>(c, s, cur, N, ts, Pb, Vb, Ab, del.t, del.p, del.a, del.w, th, tq, tg);   // :87-90
-    else onboard_fallback<R>(c, del.p, th, tq, tg);                               // :91-94
-    if (log_target != nullptr) for (int i = 0; i < 3; ++i) log_target[((size_t)step * B + b) * 3 + i] = tg[i];
-    if (log_delayed_time != nullptr) log_delayed_time[(size_t)step * B + b] = del.t;
-    if (th == (R)0) ++zeros;
-    simulator_step<R>(m, d.p, d.v, d.a, d.w, d.t, th, tq, dt, sim_dt, d.wd);      // :95
+    edge_step<R>(c, m, s, cur, lat, depth, early_load != 0 && step + 1 < nsteps, N, ts, Pb, Vb, Ab, d, dt, sim_dt, zeros, th, tq,
+                 [&](const R* tg, double delayed_t) {
+                   if (log_target != nullptr) for (int i = 0; i < 3; ++i) log_target[((size_t)step * B + b) * 3 + i] = tg[i];
+                   if (log_delayed_time != nullptr) log_delayed_time[(size_t)step * B + b] = delayed_t;
+                 });
   });
   d.store(b, pos, vel, att, omega, time);
   store_onboard<R>(onboard_state + (size_t)b * SE3MPC_ONBOARD_STATE_WORDS, s);

@@ -1103,6 +1103,39 @@ class Ops:
                            self.be.stream())
         return logs
 
+    def monte_carlo_edge(self, params: Params, op: OnboardParams, sp: SimulatorParams, onboard_state, buf, time, pos, vel, att, omega, goal,
+                         cycles: int, substeps: int, sim_dt: float, wind=None, first_cycle: int = 0, zero_thrust_steps=None,
+                         want_last_plan: bool = False):
+        """se3mpc_monte_carlo_edge_*: `cycles` x (solve from the drone's own state, `substeps` steps of :meth:`edge_loop` against the fresh plan)
+        for B drones in ONE launch, in place on (onboard_state (B, 14), the latency_buffer() `buf`, time, pos, vel, att, omega);
+        zero_thrust_steps: None or int32 (B,) counters that are incremented.  The plan's stamps count from `first_cycle`: a second call with
+        first_cycle = the cycles already flown continues a run on the same operands.  -> dict(overflowed, x, accelerations, info) as
+        :meth:`monte_carlo` (not 0: repeat the run with solve + edge_loop launches)."""
+        B = pos.shape[0]
+        suf = self.be.suffix(pos)
+        self._drone_state(B, suf, pos, vel, att, omega, goal=goal)
+        self._clock(time, B, "time")
+        self._onboard_record(onboard_state, B)
+        depth, ring, rt, lst = self._latency(buf, B, suf)
+        w_stride = self._wind(wind, B, suf)
+        if zero_thrust_steps is not None:
+            self.be.check(zero_thrust_steps, "zero_thrust_steps")
+            if tuple(zero_thrust_steps.shape) != (B,) or zero_thrust_steps.dtype != self.be.empty((0,), "i32").dtype:
+                raise ValueError(f"zero_thrust_steps: int32 ({B},)")
+        N = params.horizon
+        over = self.be.empty((1,), "i32")
+        X = self.be.empty((B, 9 * N), suf) if want_last_plan else None
+        acc = self.be.empty((B, N, 3), suf) if want_last_plan else None
+        info = self.be.empty((B * INFO_DTYPE.itemsize,), "u8") if want_last_plan else None
+        self.lib.loop_call("monte_carlo_edge", suf, params, op, sp, B, int(cycles), int(substeps), float(sim_dt), int(first_cycle), self.be.ptr(goal),
+                           self.be.ptr(wind), w_stride, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega),
+                           self.be.ptr(onboard_state), depth, ring, rt, lst, self.be.ptr(zero_thrust_steps), self.be.ptr(X), self.be.ptr(acc),
+                           self.be.ptr(info), self.be.ptr(over), self.be.stream())
+        out = dict(overflowed=over)
+        if want_last_plan:
+            out.update(x=X, accelerations=acc, info=info)
+        return out
+
     # ------------------------------------------------------------------ MotorMixer and motor model (per-drone rows)
     def _mixer_record(self, state, B):
         self.be.check(state, "mixer state")

@@ -1008,6 +1008,31 @@ int se3mpc_edge_loop_f64(const se3mpc_onboard_params* op, const se3mpc_simulator
  * Any other value: SE3MPC_ERR_PARAM. */
 int se3mpc_set_edge_loop_variant(int variant);
 
+/* The receding-horizon Monte-Carlo on the edge loop in ONE launch: for each of B drones, `cycles` times { se3mpc_solve_*
+ * from the drone's own (pos, vel) with the reference's cold start; `substeps` x the step of se3mpc_edge_loop_* (latency push ->
+ * compute_control_command -> DroneSimulator.step at sim_dt) against the fresh plan, whose row k is stamped ((first_cycle + cycle) * substeps
+ * * sim_dt) + k * params->dt }.  The same code as the two entry points it fuses, hence the same bits as alternating them
+ * (ClosedLoopMonteCarlo.run_edge) -- without 2 x cycles kernel boundaries.  All cross-cycle state is the caller's, so a second call with
+ * first_cycle = the cycles already flown continues a run bit for bit.  goal, wind, wind_stride, time, pos, vel, att, omega, X_last, acc_last,
+ * info_last, overflowed as se3mpc_monte_carlo_*; onboard_state [B][SE3MPC_ONBOARD_STATE_WORDS], depth, ring, ring_time, latency_state and
+ * zero_thrust_steps (NULL, or int32 [B] counters that are incremented) as se3mpc_edge_loop_* (depth = 0: no buffer, the three may be NULL).
+ * Argument rules, in this order: a NULL parameter struct: SE3MPC_ERR_NULL; parameters that se3mpc_check_params, se3mpc_edge_loop_* (onboard,
+ * simulator) reject: their codes; B, cycles, substeps or first_cycle < 0, horizon > 64, depth outside [0, SE3MPC_LATENCY_MAX_DEPTH],
+ * (first_cycle + cycles) * substeps beyond an int: SE3MPC_ERR_SHAPE; a non-finite sim_dt: SE3MPC_ERR_PARAM; wind with a wind_stride that is
+ * neither 0 nor >= 3: SE3MPC_ERR_SHAPE; B = 0: a no-op; then a NULL time, pos, vel, att, omega, onboard_state or overflowed, a NULL goal when
+ * the parameters have one, a NULL ring, ring_time or latency_state when depth > 0: SE3MPC_ERR_NULL.  A rejected call launches nothing;
+ * overflowed is zeroed on the stream before the launch. */
+int se3mpc_monte_carlo_edge_f32(const se3mpc_params* p, const se3mpc_onboard_params* op, const se3mpc_simulator_params* sp, int B, int cycles,
+                                int substeps, double sim_dt, int first_cycle, const float* goal, const float* wind, long long wind_stride,
+                                double* time, float* pos, float* vel, float* att, float* omega, double* onboard_state, int depth, float* ring,
+                                double* ring_time, double* latency_state, int32_t* zero_thrust_steps, float* X_last, float* acc_last,
+                                se3mpc_solve_info* info_last, int32_t* overflowed, void* stream);
+int se3mpc_monte_carlo_edge_f64(const se3mpc_params* p, const se3mpc_onboard_params* op, const se3mpc_simulator_params* sp, int B, int cycles,
+                                int substeps, double sim_dt, int first_cycle, const double* goal, const double* wind, long long wind_stride,
+                                double* time, double* pos, double* vel, double* att, double* omega, double* onboard_state, int depth,
+                                double* ring, double* ring_time, double* latency_state, int32_t* zero_thrust_steps, double* X_last,
+                                double* acc_last, se3mpc_solve_info* info_last, int32_t* overflowed, void* stream);
+
 /* ------------------------------------------------------------------ problem layout: [b][row]
  * The batched solve: replaces _solve_se3_mpc (planner.py:230-280) = cold start (or a caller
  * x0), box, scipy.optimize.minimize(method="L-BFGS-B", jac=..., bounds=..., maxiter, gtol,

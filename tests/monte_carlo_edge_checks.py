@@ -1,0 +1,209 @@
+"""What the CPU (host emulation) and GPU suites share for se3mpc_monte_carlo_edge_* / ClosedLoopMonteCarlo.run_edge_fused: the one-launch Monte-Carlo
+on the reference's edge loop (latency buffer -> OnboardController -> simulator) must give the BYTES of the chain it fuses
+(ClosedLoopMonteCarlo.run_edge: se3mpc_solve_* + se3mpc_edge_loop_* per cycle), which the kernel under test never touches.  No tolerance
+anywhere.  The chain's results are computed once per (backend, dtype, shape, configuration) and shared.  Scene and sim_dt: those of
+edge_checks.check_run_edge (rng seed 11, 0.0025), which the suite already flies finite at depths 0, 2 and 5; the wind rows are drawn behind them."""
+import numpy as np
+
+from dart_planner_amd.capi import Params
+from dart_planner_amd.control.closed_loop import ClosedLoopMonteCarlo
+
+CYCLES, SIM_DT = 6, 0.0025
+SHAPES = [(6, 19), (13, 5), (30, 3), (33, 2)]          # (N, B): the solver's group sizes 8 / 16 / 32 / 64, a partly filled last wavefront
+GPU_SHAPES = SHAPES + [(6, 130)]                      # more than one workgroup, ring rows wider than a wavefront
+DEPTHS = (0, 1, 2, 5, 9)
+# substeps 4: every ring wraps inside the run and the stale-state zero command of depth 5 / 9 falls in cycle 1 / 2; 10: depth 5's falls in cycle 0
+SUBSTEPS = (4, 10)
+WINDS = ("rows", None, "shared")                      # (B, 3), None, (3,)
+STATE_KEYS = ("pos", "vel", "att", "omega", "time", "onboard_state", "zero_thrust_steps")
+LATENCY_KEYS = ("state", "ring", "ring_time")
+
+
+def scene(B):
+    rng = np.random.default_rng(11)
+    p0 = rng.uniform(-1, 1, (B, 3)) + [0, 0, 2]
+    v0 = rng.normal(0, 0.2, (B, 3))
+    goal = rng.uniform(-3, 3, (B, 3)) + [0, 0, 2]
+    wind = rng.normal(0, 1, (B, 3))
+    return p0, v0, goal, wind
+
+
+def _operands(h, N, B, wind):
+    p0, v0, goal, w = (h.prob(a) for a in scene(B))
+    mc = ClosedLoopMonteCarlo(h.ops, Params.reference_defaults(horizon=N))
+    return mc, (p0, v0, goal), {"rows": w, None: None, "shared": w[0].contiguous()}[wind]
+
+
+def _host(h, out, depth):
+    res = {k: np.array(h.to_host(out[k])) for k in STATE_KEYS}
+    if depth > 0:
+        res.update({"latency_" + k: np.array(h.to_host(out["latency"][k])) for k in LATENCY_KEYS})
+    return res
+
+
+_chain = {}
+
+
+def chain(h, N, B, depth, substeps, wind="rows", cycles=CYCLES):
+    """ClosedLoopMonteCarlo.run_edge for the configuration, as host arrays (computed once, never written)."""
+    key = (id(h.ops), np.dtype(h.dt).name, N, B, depth, substeps, wind, cycles)
+    if key not in _chain:
+        mc, args, w = _operands(h, N, B, wind)
+        res = _host(h, mc.run_edge(*args, cycles, substeps, SIM_DT, latency_depth=depth, wind=w), depth)
+        for v in res.values():
+            v.setflags(write=False)
+        _chain[key] = res
+    return _chain[key]
+
+
+def same_bits(a, b, what):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
+    assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), f"{what}: {int((a.view(np.uint8) != b.view(np.uint8)).sum())} bytes differ"
+
+
+def same_run(got, ref, what):
+    assert sorted(got) == sorted(ref), (what, sorted(got), sorted(ref))
+    for key in ref:
+        same_bits(got[key], ref[key], f"{what}: {key}")
+
+
+def check_equals_chain(h, N, B, depth, substeps, wind="rows", last_plan=False):
+    """run_edge_fused gives the bytes of run_edge: the drones' state, the clocks, the onboard records, the counters and -- with a buffer -- the
+    latency records and the whole ring; with `last_plan` also the last cycle's plan = a solve from the chain's state after CYCLES - 1 cycles."""
+    ref = chain(h, N, B, depth, substeps, wind)
+    mc, args, w = _operands(h, N, B, wind)
+    got = mc.run_edge_fused(*args, CYCLES, substeps, SIM_DT, latency_depth=depth, wind=w, want_last_plan=last_plan)
+    assert got["logs"] == [] and got["latency"]["depth"] == depth and "controller_state" not in got
+    same_run(_host(h, got, depth), ref, f"N={N} B={B} depth={depth} substeps={substeps} wind={wind}")
+    if not last_plan:
+        assert got["last_plan"] is None
+        return
+    x = h.to_host(got["last_plan"]["x"])
+    assert x.shape == (B, 9 * N)
+    before = chain(h, N, B, depth, substeps, wind, cycles=CYCLES - 1)
+    sol = h.ops.solve(mc.params, h.to_dev(before["pos"].copy()), h.to_dev(before["vel"].copy()), args[2], want_trajectory="accelerations")
+    same_bits(x, h.to_host(sol["x"]), "last_plan x")
+    same_bits(h.to_host(got["last_plan"]["accelerations"]), h.to_host(sol["accelerations"]), "last_plan accelerations")
+
+
+def _fresh(h, N, B, depth):
+    """Fresh operands of Ops.monte_carlo_edge, as run_edge_fused makes them -> (positional arguments up to goal, the counters)."""
+    import torch
+    ops = h.ops
+    mc, (p0, v0, goal), w = _operands(h, N, B, "rows")
+    suf = "f64" if h.dt == np.float64 else "f32"
+    st, buf = ops.onboard_state(B), ops.latency_buffer(B, depth, suf)
+    time = h.to_dev(np.zeros(B))
+    zeros = h.to_dev(np.zeros(B, dtype=np.int32))
+    fl = (time, p0.clone(), v0.clone(), torch.zeros_like(p0), torch.zeros_like(p0))
+    return mc, (mc.params, ops.lib.onboard_default_params(), mc.simulator, st, buf, *fl, goal), w, zeros
+
+
+def _ops_result(h, a, zeros, depth):
+    out = dict(onboard_state=a[3], latency=a[4], time=a[5], pos=a[6], vel=a[7], att=a[8], omega=a[9], zero_thrust_steps=zeros)
+    return _host(h, out, depth)
+
+
+def check_run_continues(h, N, B, depth, substeps):
+    """Ops.monte_carlo_edge: one launch of CYCLES cycles == a launch of 2 (first_cycle=0) followed by one of CYCLES - 2 (first_cycle=2) on the same
+    operands, as bytes on everything check_equals_chain compares; and both are the chain."""
+    ops = h.ops
+    _, a, w, zeros = _fresh(h, N, B, depth)
+    one = ops.monte_carlo_edge(*a, CYCLES, substeps, SIM_DT, wind=w, zero_thrust_steps=zeros)
+    assert sorted(one) == ["overflowed"] and int(h.to_host(one["overflowed"])[0]) == 0
+    whole = _ops_result(h, a, zeros, depth)
+    _, a, w, zeros = _fresh(h, N, B, depth)
+    for first, n in ((0, 2), (2, CYCLES - 2)):
+        part = ops.monte_carlo_edge(*a, n, substeps, SIM_DT, wind=w, first_cycle=first, zero_thrust_steps=zeros)
+        assert int(h.to_host(part["overflowed"])[0]) == 0
+    split = _ops_result(h, a, zeros, depth)
+    same_run(split, whole, f"2 + {CYCLES - 2} cycles against {CYCLES}, depth {depth}")
+    same_run(whole, chain(h, N, B, depth, substeps), f"{CYCLES} cycles against the chain, depth {depth}")
+
+
+def check_not_vacuous(h, N, B, substeps):
+    """Conditions on the CHAIN's results (never on the code under test) under which the byte comparisons say something: nothing blows up, every
+    drone gets its stale-state zero command with a buffer, the buffers fill and count, and the delay changes the flight."""
+    runs = {d: chain(h, N, B, d, substeps) for d in DEPTHS}
+    steps = CYCLES * substeps
+    for d, r in runs.items():
+        for key, v in r.items():
+            assert np.isfinite(v).all(), (d, key)
+        if d >= 1:
+            assert (r["zero_thrust_steps"] >= 1).all(), (d, r["zero_thrust_steps"])
+            assert (r["latency_state"][:, 2] == steps).all() and (r["latency_state"][:, 0] == min(d, steps)).all(), (d, r["latency_state"])
+        else:
+            assert not any(k.startswith("latency_") for k in r)
+    assert (runs[5]["pos"] != runs[0]["pos"]).any(axis=1).all(), "a drone flies the same with and without the delay"
+    print(f"N={N} B={B} substeps={substeps} {np.dtype(h.dt).name}: zero-thrust steps "
+          + ", ".join(f"depth {d}: {int(r['zero_thrust_steps'].min())}..{int(r['zero_thrust_steps'].max())}" for d, r in runs.items())
+          + f"; |pos(depth 5) - pos(depth 0)| >= {np.abs(runs[5]['pos'] - runs[0]['pos']).max(axis=1).min():.3g}")
+
+
+def check_argument_rules(h):
+    """Every rule of include/se3mpc.h returns its code and launches nothing (the overflow counter keeps its sentinel: an accepted call zeroes it
+    on the stream before its launch); B = 0 is a no-op."""
+    import torch
+    ops, lib = h.ops, h.ops.lib
+    suf = "f32" if h.dt == np.float32 else "f64"
+    NULL, SHAPE, PARAM = -1, -3, -4                                             # SE3MPC_ERR_NULL, _SHAPE, _PARAM (include/se3mpc.h)
+    B, depth = 3, 2
+    prm, op, sp = Params.reference_defaults(), lib.onboard_default_params(), lib.simulator_default_params()
+    assert prm.has_goal
+    z = lambda *s: h.prob(np.zeros(s))
+    d = lambda *s: h.to_dev(np.zeros(s))
+    time, st, lst, rt = d(B), d(B, 14), d(B, 4), d(depth, B)
+    ring = z(depth, 12, B)
+    over = h.to_dev(np.full(1, 7, np.int32))
+    zeros = h.to_dev(np.zeros(B, np.int32))
+    pos, vel, att, om, goal, wind = z(B, 3), z(B, 3), z(B, 3), z(B, 3), z(B, 3), z(B, 3)
+    keep = (time, st, lst, rt, ring, over, zeros, pos, vel, att, om, goal, wind)
+    ptr = ops.be.ptr
+    default = dict(prm=prm, op=op, sp=sp, B=B, cycles=1, substeps=2, sim_dt=0.01, first=0, goal=ptr(goal), wind=0, wstride=0, time=ptr(time), pos=ptr(pos),
+                   vel=ptr(vel), att=ptr(att), omega=ptr(om), st=ptr(st), depth=depth, ring=ptr(ring), rt=ptr(rt), lst=ptr(lst), zeros=ptr(zeros), over=ptr(over))
+
+    def status(**kw):
+        a = dict(default, **kw)
+        assert not set(kw) - set(default)
+        return lib.loop_status("monte_carlo_edge", suf, a["prm"], a["op"], a["sp"], a["B"], a["cycles"], a["substeps"], a["sim_dt"], a["first"], a["goal"],
+                               a["wind"], a["wstride"], a["time"], a["pos"], a["vel"], a["att"], a["omega"], a["st"], a["depth"], a["ring"], a["rt"], a["lst"],
+                               a["zeros"], 0, 0, 0, a["over"], ops.be.stream())
+
+    def broken(make, **fields):
+        p = make()
+        for k, v in fields.items():
+            setattr(p, k, v)
+        return p
+
+    rejected = [
+        (NULL, dict(prm=None)), (NULL, dict(op=None)), (NULL, dict(sp=None)),
+        (NULL, dict(time=0)), (NULL, dict(pos=0)), (NULL, dict(vel=0)), (NULL, dict(att=0)), (NULL, dict(omega=0)), (NULL, dict(st=0)), (NULL, dict(over=0)),
+        (NULL, dict(goal=0)), (NULL, dict(ring=0)), (NULL, dict(rt=0)), (NULL, dict(lst=0)),
+        (PARAM, dict(prm=Params.reference_defaults(mass=float("nan")))), (PARAM, dict(op=broken(lib.onboard_default_params, g=float("inf")))),
+        (PARAM, dict(op=broken(lib.onboard_default_params, mass=0.0))), (PARAM, dict(sp=broken(lib.simulator_default_params, mass=-1.0))),
+        (PARAM, dict(sim_dt=float("nan"))), (PARAM, dict(sim_dt=float("inf"))),
+        (SHAPE, dict(B=-1)), (SHAPE, dict(cycles=-1)), (SHAPE, dict(substeps=-1)), (SHAPE, dict(first=-1)),
+        (SHAPE, dict(depth=-1)), (SHAPE, dict(depth=1001)),
+        (SHAPE, dict(wind=ptr(wind), wstride=1)), (SHAPE, dict(wind=ptr(wind), wstride=2)), (SHAPE, dict(wind=ptr(wind), wstride=-3)),
+        (SHAPE, dict(first=2 ** 30, cycles=2 ** 30 - 1, substeps=2)), (SHAPE, dict(first=0, cycles=2 ** 16, substeps=2 ** 15)),
+        # a horizon beyond 64 never reaches the kernel's own rule: se3mpc_check_params rejects it first, with its code
+        (lib.check_params(Params.reference_defaults(horizon=65)), dict(prm=Params.reference_defaults(horizon=65))),
+    ]
+    for code, kw in rejected:
+        assert code < 0 and status(**kw) == code, (code, kw, status(**kw))
+    if hasattr(torch, "cuda") and torch.cuda.is_available():
+        torch.cuda.synchronize()
+    assert int(h.to_host(over)[0]) == 7, "a rejected call touched the overflow counter"
+    for a in (time, st, lst, rt, ring, pos, vel, att, om):
+        assert not np.asarray(h.to_host(a)).any(), "a rejected call wrote an operand"
+    # accepted: B = 0 with nothing else there; no buffer with its three operands NULL; wind strides 0 and 3; the largest step count
+    assert status(B=0, time=0, pos=0, vel=0, att=0, omega=0, st=0, over=0, goal=0, ring=0, rt=0, lst=0) == 0
+    assert int(h.to_host(over)[0]) == 7
+    assert status(depth=0, ring=0, rt=0, lst=0, zeros=0) == 0
+    assert status(wind=ptr(wind), wstride=0) == 0 and status(wind=ptr(wind), wstride=3) == 0
+    assert status(cycles=0, first=2 ** 31 - 1, substeps=1) == 0 and status() == 0
+    if hasattr(torch, "cuda") and torch.cuda.is_available():
+        torch.cuda.synchronize()
+    assert int(h.to_host(over)[0]) == 0
+    del keep

@@ -1,0 +1,65 @@
+"""GPU suite (`-m gpu`): se3mpc_monte_carlo_edge_* / ClosedLoopMonteCarlo.run_edge_fused on a real MI355X: the one-launch Monte-Carlo on the
+reference's edge loop gives the bytes of the chain of launches it fuses -- the checks of tests/monte_carlo_edge_checks.py (at most 130 drones x
+6 cycles x 10 steps)."""
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+import parity_checks as pc  # noqa: E402
+import monte_carlo_edge_checks as ec  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def gpu_ops():
+    import torch
+    assert torch.cuda.is_available(), "the gpu suite needs an MI355X"
+    from dart_planner_amd.ops import Ops, TorchBackend
+    ops = Ops(TorchBackend("cuda:0"))
+    assert ops.lib.device_count() >= 1, "no gfx950 device visible to libse3mpc"
+    assert os.path.basename(ops.lib.path) == "libse3mpc.so"
+    return ops
+
+
+def harness(ops, dt):
+    import torch
+    return pc.Harness(ops, lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0"), lambda a: a.detach().cpu().numpy(), dt)
+
+
+DTYPES = [np.float64, np.float32]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("N,B", ec.SHAPES)
+@pytest.mark.parametrize("substeps", ec.SUBSTEPS)
+def test_chain_conditions_are_not_vacuous(gpu_ops, dt, N, B, substeps):
+    ec.check_not_vacuous(harness(gpu_ops, dt), N, B, substeps)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("N,B", ec.GPU_SHAPES)
+@pytest.mark.parametrize("substeps", ec.SUBSTEPS)
+@pytest.mark.parametrize("depth", ec.DEPTHS)
+def test_one_launch_equals_the_chain_byte_for_byte(gpu_ops, dt, N, B, substeps, depth):
+    ec.check_equals_chain(harness(gpu_ops, dt), N, B, depth, substeps, last_plan=depth == 2)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("N,B", ec.GPU_SHAPES)
+@pytest.mark.parametrize("wind", [None, "shared"])
+def test_one_launch_equals_the_chain_without_and_with_shared_wind(gpu_ops, dt, N, B, wind):
+    ec.check_equals_chain(harness(gpu_ops, dt), N, B, 5, 4, wind=wind)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("N,B", ec.GPU_SHAPES)
+@pytest.mark.parametrize("depth", [1, 5])
+def test_a_second_launch_continues_the_first(gpu_ops, dt, N, B, depth):
+    ec.check_run_continues(harness(gpu_ops, dt), N, B, depth, 4)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_argument_rules(gpu_ops, dt):
+    ec.check_argument_rules(harness(gpu_ops, dt))

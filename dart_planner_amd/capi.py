@@ -355,6 +355,8 @@ _LOOP_TYPED_API = {
                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mppi_closed_loop_staged": [_PP, _CP, _SP, _MP, _XP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I,
                                 _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P],
+    "mppi_closed_loop_edge": [_PP, _OP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _D, _P,
+                              _LL, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 _PLAIN_API = {
     "se3mpc_controller_default_params": (C.c_int, [_CP]),

@@ -16,6 +16,8 @@ one-launch MPPI Monte-Carlo, where the clearance to the spheres is measured too 
 ``run_fused``, ``run_mppi_fused`` and ``capture`` do not have them.  ``run_edge`` flies the reference's OTHER edge loop (edge/main.py:21-112) under the
 same planner: a latency buffer between the drone's state and its controller, and the cascaded-PID OnboardController in place of the geometric one
 (``se3mpc_edge_loop_*``); ``run_edge_fused`` flies it inside one launch (``se3mpc_monte_carlo_edge_*``).
+``run_mppi_edge`` / ``run_mppi_edge_fused`` fly that edge loop under the MPPI planner, as a chain and in one launch
+(``se3mpc_mppi_closed_loop_edge_*``): the one form where the delay and the obstacle clearance meet.
 """
 import math
 from typing import Optional
@@ -344,6 +346,83 @@ class ClosedLoopMonteCarlo:
         logs = [dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"])] if log else []
         more = dict(followed=out["followed"]) if smoother is not None else {}
         return self._result(st, sm, fl, logs=logs, U=U, cost=out["cost"], trace=out["trace"], clearance=out["clearance"], mixer_state=mx, **more)
+
+    def run_mppi_edge(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
+                      seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None, nominal=None,
+                      latency_depth: int = 5, onboard: Optional[OnboardParams] = None, log: bool = False):
+        """The receding-horizon Monte-Carlo with MPPI as the planner on the reference's edge loop (edge/main.py:80-95), as a chain of two
+        launches per cycle: ``se3mpc_mppi_closed_loop_*`` as the planner alone (one cycle, no simulator steps, on a scratch geometric-controller
+        record it leaves untouched; arguments and shift rule as :meth:`run_mppi`), then ONE ``se3mpc_edge_loop_*`` launch of `substeps` x
+        (latency push -> OnboardController.compute_control_command -> DroneSimulator.step) that reads the handed-over plan in place
+        (latency_depth, onboard and the stale-state zero command as :meth:`run_edge`).
+        -> the keys of :meth:`run_edge` (pos, vel, att, omega, time, onboard_state, latency, zero_thrust_steps, logs) plus U (B, N, 3) = the
+        next cycle's nominal, cost (B,) at the last cycle's nominal, trace (B, cycles, iters) and clearance = None (no launch of this chain
+        measures it); logs = [(planner outputs, edge-loop outputs)] per cycle if `log`.
+        :meth:`run_mppi_edge_fused` is the same run in one launch, with the clearance (``se3mpc_mppi_closed_loop_edge_*``; measured at 0.92 - 0.97 of
+        this chain's time for 256 drones and 0.98 - 1.05 for 4096 at 256 samples x 8 iterations, N = 30: DESIGN.md 5.8e; other shapes: not measured);
+        this chain stays the form with per-step logs."""
+        import torch
+        ops, prm = self.ops, self.params
+        B, N = p0.shape[0], prm.horizon
+        op = onboard if onboard is not None else ops.lib.onboard_default_params()
+        scratch, _, fl = self._start(p0, v0)                  # the planner's entry point wants a controller record; with no steps it never reads it
+        st = ops.onboard_state(B)
+        buf = ops.latency_buffer(B, latency_depth, ops.be.suffix(p0))
+        zeros = torch.zeros(B, dtype=torch.int32, device=ops.be.device)
+        U = self._mppi_start(p0, nominal)
+        sh = self.resolve_shift(substeps, sim_dt, shift)
+        k = torch.arange(N, dtype=torch.float64, device=ops.be.device)
+        logs, traces, out = [], [], None
+        for c in range(cycles):
+            out = ops.mppi_closed_loop(prm, self.controller, self.simulator, scratch, *fl, goal, U, 1, 0, sim_dt, n_samples, iters, sigma, temperature,
+                                       seed=seed, cycle_base=c, shift=sh, spheres=spheres, obstacle_weight=obstacle_weight, wind=wind, want_plan=True,
+                                       want_clearance=False)
+            traces.append(out["trace"])
+            flat = out["plan_last"].view(B, 9 * N)                # (P, V, A) of drone b: 3N values each, 9N apart from drone to drone
+            flown = ops.edge_loop(op, self.simulator, st, buf, *fl, (c * substeps * sim_dt) + k * prm.dt, flat, flat[:, 3 * N:], flat[:, 6 * N:],
+                                  nsteps=substeps, sim_dt=sim_dt, strides=(9 * N, 9 * N, 9 * N), wind=wind, log=log, zero_thrust_steps=zeros)
+            if log:
+                logs.append((out, flown))
+        trace = torch.cat(traces, dim=1) if traces else torch.zeros(B, 0, max(int(iters), 0), dtype=p0.dtype, device=ops.be.device)
+        time, pos, vel, att, om = fl
+        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, onboard_state=st, latency=buf, zero_thrust_steps=zeros, logs=logs, U=U,
+                    cost=None if out is None else out["cost"], trace=trace, clearance=None)
+
+    def run_mppi_edge_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float,
+                            temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None,
+                            nominal=None, latency_depth: int = 5, onboard: Optional[OnboardParams] = None, want_last_plan: bool = False):
+        """:meth:`run_mppi_edge` in ONE launch (``se3mpc_mppi_closed_loop_edge_*``): every cycle's MPPI iterations and its
+        `substeps` x (latency push -> OnboardController -> DroneSimulator.step) inside one kernel, the plan never leaving the chip, where
+        :meth:`run_mppi_edge` makes two launches per cycle -- and with ``clearance`` (B,) filled in whenever there are spheres, which the chain
+        cannot measure: the one form that says what the delay costs the sampling planner in clearance.  Same code, same bits, same arguments
+        and shift rule as :meth:`run_mppi_edge` (no logs); the same result keys, plus plan_last (B, 3, N, 3) = the last cycle's plan if
+        `want_last_plan`, else None.  All cross-cycle state is in the returned operands (U, onboard_state, latency, time, zero_thrust_steps,
+        clearance), so ``Ops.mppi_closed_loop_edge`` with ``cycle_base=cycles`` continues the run.
+
+        Measured on an MI355X (``profiles/mppi_closed_loop_edge.json``; 256 samples, 8 iterations, N = 30, 33 cycles x 15 steps, 0 and 16
+        spheres, depth 0 and 5): at 256 drones 10.95 - 19.16 ms (float32) / 20.71 - 29.24 ms (float64) against 11.78 - 20.15 / 21.54 - 30.05 ms for the 66
+        launches of :meth:`run_mppi_edge` -- 0.92 - 0.97 of the chain's time; at 4096 drones 90.8 - 125.1 / 236.9 - 304.1 ms against 88.0 - 125.8 / 232.0 -
+        300.1 ms -- 1.02 - 1.05 without spheres, 0.98 - 1.01 with 16 (one lane per workgroup flies the act phase while the others wait; the chain's
+        planner is the same three / two wavefronts per SIMD kernel, so the gap is small).  Use this form for hundreds of drones, and at any size when
+        the clearance or one enqueue is what you need; for thousands of drones without spheres :meth:`run_mppi_edge` is a few per cent faster.  Other
+        batch sizes, sample counts and horizons: not measured; :meth:`run_mppi_edge` stays the form with per-step logs."""
+        import torch
+        ops = self.ops
+        B = p0.shape[0]
+        op = onboard if onboard is not None else ops.lib.onboard_default_params()
+        # the flight state of _start, without the geometric controller's records: this loop has none
+        fl = (torch.zeros(B, dtype=torch.float64, device=ops.be.device), p0.clone(), v0.clone(), torch.zeros_like(p0), torch.zeros_like(p0))
+        st = ops.onboard_state(B)
+        buf = ops.latency_buffer(B, latency_depth, ops.be.suffix(p0))
+        zeros = torch.zeros(B, dtype=torch.int32, device=ops.be.device)
+        U = self._mppi_start(p0, nominal)
+        sh = self.resolve_shift(substeps, sim_dt, shift)
+        out = ops.mppi_closed_loop_edge(self.params, op, self.simulator, st, buf, *fl, goal, U, cycles, substeps, sim_dt, n_samples, iters, sigma,
+                                        temperature, seed=seed, cycle_base=0, shift=sh, spheres=spheres, obstacle_weight=obstacle_weight, wind=wind,
+                                        want_plan=want_last_plan, zero_thrust_steps=zeros)
+        time, pos, vel, att, om = fl
+        return dict(pos=pos, vel=vel, att=att, omega=om, time=time, onboard_state=st, latency=buf, zero_thrust_steps=zeros, logs=[], U=U,
+                    cost=out["cost"], trace=out["trace"], clearance=out["clearance"], plan_last=out["plan_last"])
 
     def capture(self, B: int, dtype, cycles: int, substeps: int, sim_dt: float, with_wind: bool = True, smoother=None, mixer=None,
                 motor_health=None):

@@ -9,98 +9,23 @@
 // the chip).
 //
 // Mapping, LDS image and register budget as monte_carlo.hip; behind each drone's block lie the two records and the zero-thrust counter
-// (EdgeRecords).  The ring stays the HBM operand of se3mpc_edge_loop_*, indexed by the drone: the act phase's one lane loads the entry a push
+// (EdgeRecords; the act phase is edge_act of edge_act_device.hpp, shared with mppi_closed_loop_edge.hip).  The ring stays the HBM operand of se3mpc_edge_loop_*, indexed by the drone: the act phase's one lane loads the entry a push
 // pops one step ahead (LatencyLane), as every edge-loop launch does.
 #include "solve_device.hpp"
 #pragma clang fp contract(off)
-#include "edge_device.hpp"
+#include "edge_act_device.hpp"
 
 namespace se3mpc {
 
-// What the kernel keeps per drone behind its DroneBlock, at mc_consts_offset: the onboard record and the latency record (doubles, as in
-// memory) and the steps whose commanded thrust was exactly 0.  DroneBlock::ctrl (the geometric controller's 12 words) is not used here: the
-// onboard record has 14.
-struct EdgeRecords {
-  __host__ __device__ static constexpr size_t counter_offset() { return (size_t)(SE3MPC_ONBOARD_STATE_WORDS + SE3MPC_LATENCY_STATE_WORDS) * sizeof(double); }
-  __host__ __device__ static constexpr size_t bytes() { return (counter_offset() + sizeof(int) + 15) / 16 * 16; }
-};
+// Behind each drone's DroneBlock, at mc_consts_offset: its EdgeRecords (edge_act_device.hpp)
 template <typename IO>
 __host__ __device__ constexpr size_t edge_group_bytes(int G) { return mc_consts_offset<IO>(G) + EdgeRecords::bytes(); }
 
-template <typename IO>
-struct EdgeBlock {
-  DroneBlock<IO> d;
-  double *orec, *lrec;     // onboard record [SE3MPC_ONBOARD_STATE_WORDS], latency record [SE3MPC_LATENCY_STATE_WORDS]
-  int* zeros;
-};
 // Group grp's block.  Built again inside each phase, as mc_block.
 template <typename IO, int G>
 __device__ __forceinline__ EdgeBlock<IO> edge_block(unsigned char* lds_raw, size_t solver_lds, int grp) {
   unsigned char* gb = lds_raw + solver_lds + (size_t)grp * edge_group_bytes<IO>(G);
-  EdgeBlock<IO> b;
-  b.d = drone_block<IO>(gb, G, mc_plan_offset<IO>(G), mc_plan_offset<IO>(G) + (size_t)9 * G * sizeof(IO));
-  b.orec = reinterpret_cast<double*>(gb + mc_consts_offset<IO>(G));
-  b.lrec = b.orec + SE3MPC_ONBOARD_STATE_WORDS;
-  b.zeros = reinterpret_cast<int*>(gb + mc_consts_offset<IO>(G) + EdgeRecords::counter_offset());
-  return b;
-}
-
-// Drone pb's state, wind, clock and records into its block (latencyg is read only with a buffer) ...
-template <typename IO>
-__device__ __forceinline__ void edge_load(const EdgeBlock<IO>& b, int pb, const IO* __restrict__ posg, const IO* __restrict__ velg,
-                                          const IO* __restrict__ attg, const IO* __restrict__ omegag, const IO* __restrict__ windg,
-                                          long long wind_stride, const double* __restrict__ timeg, const double* __restrict__ onboardg, int depth,
-                                          const double* __restrict__ latencyg) {
-  DroneRegs<IO> r;
-  r.load(pb, posg, velg, attg, omegag, windg, wind_stride, timeg);
-  r.store(b.d);
-  for (int i = 0; i < 3; ++i) b.d.vec[12 + i] = r.wd[i];
-  for (int i = 0; i < SE3MPC_ONBOARD_STATE_WORDS; ++i) b.orec[i] = onboardg[(size_t)pb * SE3MPC_ONBOARD_STATE_WORDS + i];
-  for (int i = 0; i < SE3MPC_LATENCY_STATE_WORDS; ++i) b.lrec[i] = depth > 0 ? latencyg[(size_t)pb * SE3MPC_LATENCY_STATE_WORDS + i] : 0.0;
-  *b.zeros = 0;
-}
-// ... and back; the counter is added to the caller's
-template <typename IO>
-__device__ __forceinline__ void edge_store(const EdgeBlock<IO>& b, int pb, IO* __restrict__ posg, IO* __restrict__ velg, IO* __restrict__ attg,
-                                           IO* __restrict__ omegag, double* __restrict__ timeg, double* __restrict__ onboardg, int depth,
-                                           double* __restrict__ latencyg, int32_t* __restrict__ zero_thrust_steps) {
-  DroneRegs<IO> r;
-  r.load(b.d);
-  r.store(pb, posg, velg, attg, omegag, timeg);
-  for (int i = 0; i < SE3MPC_ONBOARD_STATE_WORDS; ++i) onboardg[(size_t)pb * SE3MPC_ONBOARD_STATE_WORDS + i] = b.orec[i];
-  if (depth > 0)
-    for (int i = 0; i < SE3MPC_LATENCY_STATE_WORDS; ++i) latencyg[(size_t)pb * SE3MPC_LATENCY_STATE_WORDS + i] = b.lrec[i];
-  if (zero_thrust_steps != nullptr) zero_thrust_steps[pb] += *b.zeros;
-}
-
-// The act phase of one cycle of the drone in block b, by ONE lane, against the N-row plan the solver has handed over: what one
-// se3mpc_edge_loop_* launch of `substeps` steps does to the drone -- the records from the block into registers, the cursor reset, the buffer's
-// begin, the steps (each but the last with the next entry loaded ahead), the buffer's end (depth 1: the previous state reaches the ring), and
-// back.  c and m by value, as fly_steps.
-template <typename IO>
-__device__ __forceinline__ void edge_act(const EdgeBlock<IO>& b, const OnboardDev<IO> c, const SimDev<IO> m, int N, int substeps, double sim_dt,
-                                         const LatRing<IO>& ring) {
-  const DroneBlock<IO>& d = b.d;
-  OnboardRegs<IO> s = load_onboard<IO>(b.orec);
-  DroneRegs<IO> r;
-  r.load(d);
-  const IO dt = (IO)sim_dt;
-  PlanCursor<IO> cur;
-  cursor_reset(cur);
-  const int depth = ring.depth;
-  LatencyLane<IO> lat;
-  lat.ring = ring;
-  if (depth > 0) lat.begin(b.lrec);
-  int zeros = 0;
-  for (int step = 0; step < substeps; ++step) {
-    IO th, tq[3];
-    edge_step<IO>(c, m, s, cur, lat, depth, step + 1 < substeps, N, d.stamps, d.planP, d.planV, d.planA, r, dt, sim_dt, zeros, th, tq,
-                  [](const IO*, double) {});
-  }
-  r.store(d);
-  store_onboard<IO>(b.orec, s);
-  if (depth > 0) lat.end(b.lrec);
-  *b.zeros += zeros;
+  return edge_block_at<IO>(drone_block<IO>(gb, G, mc_plan_offset<IO>(G), mc_plan_offset<IO>(G) + (size_t)9 * G * sizeof(IO)), gb + mc_consts_offset<IO>(G));
 }
 
 }  // namespace se3mpc
@@ -173,7 +98,8 @@ monte_carlo_edge_kernel(SolveDev q, OnboardDev<IO> onb, SimDev<IO> sim, int B, i
     group_sync<G>();
     // ---- act: `substeps` steps of the edge loop (latency push, OnboardController, simulator step) on the group's first lane
     if (k == 0 && substeps > 0)        // (no steps: the chain's edge-loop launch is a no-op that touches no record)
-      edge_act<IO>(edge_block<IO, G>(lds_raw, solver_lds, grp), onb, sim, q.N, substeps, sim_dt, LatRing<IO>{ringg, ring_timeg, depth, B, pb});
+      edge_act<IO>(edge_block<IO, G>(lds_raw, solver_lds, grp), onb, sim, q.N, substeps, sim_dt, LatRing<IO>{ringg, ring_timeg, depth, B, pb},
+                   [](int, const IO*) {});
     group_sync<G>();
   }
   if (k == 0)

@@ -1136,6 +1136,53 @@ class Ops:
             out.update(x=X, accelerations=acc, info=info)
         return out
 
+    def mppi_closed_loop_edge(self, params: Params, op: OnboardParams, sp: SimulatorParams, onboard_state, buf, time, pos, vel, att, omega, goal, U,
+                              cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
+                              seed: int = 0, cycle_base: int = 0, shift: int = 1, iter_base: int = 0, index_base: int = 0, spheres=None,
+                              obstacle_weight: float = 0.0, wind=None, want_trace: bool = True, want_plan: bool = False, clearance=None,
+                              want_clearance: bool = True, zero_thrust_steps=None):
+        """se3mpc_mppi_closed_loop_edge_*: `cycles` x (`iters` MPPI iterations from the drone's own state on its nominal as
+        :meth:`mppi_closed_loop`, the plan handed over on the chip, `substeps` steps of :meth:`edge_loop` against it, the nominal shifted by
+        `shift` rows) for B drones in ONE launch, in place on (onboard_state (B, 14), the latency_buffer() `buf`, time, pos, vel, att, omega)
+        and on the nominals U (B, N, 3); zero_thrust_steps: None or int32 (B,) counters that are added to.  goal, spheres, wind, clearance and
+        want_clearance as :meth:`mppi_closed_loop`.  All cross-cycle state is in these operands: a second call with cycle_base = the cycles
+        already flown continues a run.
+        -> dict(U, cost, trace, plan_last, clearance) as :meth:`mppi_closed_loop`."""
+        B = pos.shape[0]
+        suf = self.be.suffix(pos)
+        N = params.horizon
+        self._drone_state(B, suf, pos, vel, att, omega, goal=goal)
+        self._clock(time, B, "time")
+        self._onboard_record(onboard_state, B)
+        depth, ring, rt, lst = self._latency(buf, B, suf)
+        self.be.check(U, "U")
+        if tuple(U.shape) != (B, N, 3) or self.be.suffix(U) != suf:
+            raise ValueError(f"U: expected ({B}, {N}, 3) {suf}, got {tuple(U.shape)}")
+        w_stride = self._wind(wind, B, suf)
+        K = 0
+        if spheres is not None:
+            K = self._spheres(spheres, suf)
+        self._per_drone(B, suf, clearance=clearance)
+        if zero_thrust_steps is not None:
+            self.be.check(zero_thrust_steps, "zero_thrust_steps")
+            if tuple(zero_thrust_steps.shape) != (B,) or zero_thrust_steps.dtype != self.be.empty((0,), "i32").dtype:
+                raise ValueError(f"zero_thrust_steps: int32 ({B},)")
+        if clearance is None and want_clearance and K:
+            clearance = self.be.empty((B,), suf)
+            clearance[...] = float("inf")
+        cost = self.be.empty((B,), suf)
+        trace = self.be.empty((B, max(int(cycles), 1), max(int(iters), 1)), suf) if want_trace else None
+        plan = self.be.empty((B, 3, N, 3), suf) if want_plan else None
+        self.lib.loop_call("mppi_closed_loop_edge", suf, params, op, sp, B, int(cycles), int(substeps), float(sim_dt), int(cycle_base) & 0xFFFFFFFF,
+                           int(shift), int(n_samples), int(iters), float(sigma), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                           int(iter_base) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF, self.be.ptr(goal), self.be.ptr(spheres if K else None), K,
+                           float(obstacle_weight), self.be.ptr(wind), w_stride, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel),
+                           self.be.ptr(att), self.be.ptr(omega), self.be.ptr(onboard_state), depth, ring, rt, lst, self.be.ptr(zero_thrust_steps),
+                           self.be.ptr(U), self.be.ptr(cost), self.be.ptr(trace), self.be.ptr(plan), self.be.ptr(clearance), self.be.stream())
+        if trace is not None and (cycles <= 0 or iters <= 0):
+            trace = trace[:, :max(int(cycles), 0), :max(int(iters), 0)]
+        return dict(U=U, cost=cost, trace=trace, plan_last=plan, clearance=clearance)
+
     # ------------------------------------------------------------------ MotorMixer and motor model (per-drone rows)
     def _mixer_record(self, state, B):
         self.be.check(state, "mixer state")

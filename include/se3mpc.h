@@ -1033,6 +1033,41 @@ int se3mpc_monte_carlo_edge_f64(const se3mpc_params* p, const se3mpc_onboard_par
                                 double* ring, double* ring_time, double* latency_state, int32_t* zero_thrust_steps, double* X_last,
                                 double* acc_last, se3mpc_solve_info* info_last, int32_t* overflowed, void* stream);
 
+/* The closed-loop MPPI Monte-Carlo on the edge loop in ONE launch: se3mpc_mppi_closed_loop_* with the act phase of
+ * se3mpc_monte_carlo_edge_*.  One workgroup of min(S, 256) lanes per drone; for each of B drones, `cycles` times { plan, hand over, clearance
+ * and warm start as se3mpc_mppi_closed_loop_* (the same code, hence the same bits: Philox stream index_base + b, iteration number iter_base +
+ * C * iters + i with C = cycle_base + cycle, plan row k stamped (C * substeps * sim_dt) + k * params->dt); act: `substeps` x the step of
+ * se3mpc_edge_loop_* (latency push -> compute_control_command -> the zero-thrust count -> DroneSimulator.step at sim_dt) against the plan on
+ * the chip }.  The same code as the two entry points it fuses, hence the same bits as se3mpc_mppi_closed_loop_* with substeps = 0 followed by
+ * se3mpc_edge_loop_* on plan_last, cycle by cycle (ClosedLoopMonteCarlo.run_mppi_edge) -- and with the clearance, which that chain cannot
+ * measure.  substeps = 0: no act phase, no record, ring or counter is touched.
+ * Operands: goal, spheres, K, wind, wind_stride, time, pos, vel, att, omega, U, cost, trace, plan_last and clearance as
+ * se3mpc_mppi_closed_loop_*; onboard_state [B][SE3MPC_ONBOARD_STATE_WORDS], depth, ring [depth][12][B], ring_time [depth][B], latency_state
+ * [B][SE3MPC_LATENCY_STATE_WORDS] and zero_thrust_steps (NULL, or int32 [B] counters that are added to) as se3mpc_edge_loop_*, the ring's row
+ * width being this call's B (depth = 0: no buffer, the three may be NULL).  There is no geometric controller and no controller record.  All
+ * cross-cycle state is the caller's, so one call with cycles = C equals C calls with cycles = 1 and cycle_base = 0 .. C - 1 on the same
+ * operands, and a second call continues a run, bit for bit.  No atomics, no workspace, no allocation, no synchronise.
+ * Argument rules: a NULL parameter struct: SE3MPC_ERR_NULL; parameters that se3mpc_check_params, se3mpc_edge_loop_* (onboard, simulator)
+ * reject: their codes; cycles or substeps < 0, shift outside [0, N], depth outside [0, SE3MPC_LATENCY_MAX_DEPTH], (cycle_base + cycles) *
+ * substeps beyond an int, wind with a wind_stride that is neither 0 nor >= 3: SE3MPC_ERR_SHAPE; everything se3mpc_mppi_* rejects (B < 0, S, iters,
+ * K: SE3MPC_ERR_SHAPE; sigma, temperature, obstacle_weight: SE3MPC_ERR_PARAM); a non-finite sim_dt: SE3MPC_ERR_PARAM; B = 0 and cycles = 0 are
+ * no-ops; then a NULL time, pos, vel, att, omega, onboard_state, U or cost, a NULL goal when the parameters have one, NULL spheres when K > 0, a
+ * NULL ring, ring_time or latency_state when depth > 0: SE3MPC_ERR_NULL.  Every rejected call sets se3mpc_last_error and launches nothing. */
+int se3mpc_mppi_closed_loop_edge_f32(const se3mpc_params* p, const se3mpc_onboard_params* op, const se3mpc_simulator_params* sp, int B, int cycles,
+                                     int substeps, double sim_dt, uint32_t cycle_base, int shift, int S, int iters, double sigma,
+                                     double temperature, uint64_t seed, uint32_t iter_base, uint32_t index_base, const float* goal,
+                                     const float* spheres, int K, double obstacle_weight, const float* wind, long long wind_stride, double* time,
+                                     float* pos, float* vel, float* att, float* omega, double* onboard_state, int depth, float* ring,
+                                     double* ring_time, double* latency_state, int32_t* zero_thrust_steps, float* U, float* cost, float* trace,
+                                     float* plan_last, float* clearance, void* stream);
+int se3mpc_mppi_closed_loop_edge_f64(const se3mpc_params* p, const se3mpc_onboard_params* op, const se3mpc_simulator_params* sp, int B, int cycles,
+                                     int substeps, double sim_dt, uint32_t cycle_base, int shift, int S, int iters, double sigma,
+                                     double temperature, uint64_t seed, uint32_t iter_base, uint32_t index_base, const double* goal,
+                                     const double* spheres, int K, double obstacle_weight, const double* wind, long long wind_stride,
+                                     double* time, double* pos, double* vel, double* att, double* omega, double* onboard_state, int depth,
+                                     double* ring, double* ring_time, double* latency_state, int32_t* zero_thrust_steps, double* U, double* cost,
+                                     double* trace, double* plan_last, double* clearance, void* stream);
+
 /* ------------------------------------------------------------------ problem layout: [b][row]
  * The batched solve: replaces _solve_se3_mpc (planner.py:230-280) = cold start (or a caller
  * x0), box, scipy.optimize.minimize(method="L-BFGS-B", jac=..., bounds=..., maxiter, gtol,

@@ -1,0 +1,368 @@
+"""What the CPU (host emulation) and GPU suites share for se3mpc_mppi_closed_loop_edge_* / Ops.mppi_closed_loop_edge /
+ClosedLoopMonteCarlo.run_mppi_edge_fused: the one-launch closed-loop MPPI Monte-Carlo on the reference's edge loop (latency buffer ->
+OnboardController -> simulator) must give the BYTES of the chain it fuses (ClosedLoopMonteCarlo.run_mppi_edge: se3mpc_mppi_closed_loop_* with
+no steps + se3mpc_edge_loop_* per cycle), which runs none of the kernel under test, and the clearance that chain cannot measure must agree with
+the positions the chain logs.  No tolerance anywhere but on the clearance.  The chain's results are computed once per configuration and shared,
+read-only.
+
+The scene: rng seed 29; the planner is the one of mppi_closed_loop_staged_checks (plan step 0.1 s, sigma 1, temperature 50, obstacle weight 40
+where there are spheres, seed 17, hover nominal, the default shift rule), the edge loop the default OnboardController and simulator at 0.01 s.
+MOVES (1e-3 m, the margin of mppi_closed_loop_staged_checks and for its reason) is how far the delay must move every drone."""
+import numpy as np
+
+from mppi_closed_loop_staged_checks import MOVES
+from monte_carlo_edge_checks import same_bits, same_run
+from dart_planner_amd.capi import Params
+from dart_planner_amd.control.closed_loop import ClosedLoopMonteCarlo
+
+CYCLES, SIM_DT, ITERS = 4, 0.01, 2
+SHAPES = [(6, 5, 0, 64), (13, 4, 3, 256), (30, 3, 16, 512)]        # (N, B, K, S): one wavefront per workgroup; a full block; two sample passes and 16 spheres
+GPU_SHAPES = SHAPES + [(6, 70, 2, 64)]                            # more workgroups than one wavefront's worth of ring columns
+# The host emulation runs a 256-lane workgroup two decades slower than the device: the CPU suite sweeps the smallest shape and one like it with
+# spheres, and flies the full block once.
+EMU_SHAPES = [SHAPES[0], (6, 4, 2, 64)]
+PLAN_DT, SIGMA, LAM, W_OBS, SEED = 0.1, 1.0, 50.0, 40.0, 17
+DEPTHS = (0, 1, 2, 5)
+# substeps 4: the shift resolves to 0 and depth 5's stale-state zero command falls in cycle 1; 10: the shift is 1 and it falls in cycle 0
+SUBSTEPS = (4, 10)
+WINDS = ("rows", None, "shared")                                  # (B, 3), None, (3,)
+LONG_SUBSTEPS, LONG_CYCLES = 70, 2                                # > kPark = 64: an act phase of two chunks
+# depth 66: the buffer fills in the first chunk and its first pop -- the delayed clock steps back, the cursor searches from the start -- is step 2 of the second
+LONG_DEPTHS = (1, 5, 66)
+STATE_KEYS = ("pos", "vel", "att", "omega", "time", "onboard_state", "zero_thrust_steps")
+PLAN_KEYS = ("U", "cost", "trace")
+LATENCY_KEYS = ("state", "ring", "ring_time")
+
+
+def scene(B, K):
+    rng = np.random.default_rng(29)
+    p0 = rng.uniform(-1, 1, (B, 3)) + [0, 0, 2]
+    v0 = rng.normal(0, 0.2, (B, 3))
+    goal = rng.uniform(-3, 3, (B, 3)) + [0, 0, 2]
+    wind = rng.normal(0, 1, (B, 3))
+    spheres = np.concatenate([rng.uniform(-3, 3, (K, 3)) + [0, 0, 2], rng.uniform(0.2, 0.6, (K, 1))], axis=1)
+    return p0, v0, goal, wind, spheres
+
+
+def params(N):
+    return Params.reference_defaults(horizon=N, dt=PLAN_DT)
+
+
+def _operands(h, shape, depth, substeps, wind="rows", cycles=CYCLES):
+    """-> (mc, positional arguments, keyword arguments) of run_mppi_edge / run_mppi_edge_fused for one configuration."""
+    N, B, K, S = shape
+    p0, v0, goal, w, sph = (h.prob(a) for a in scene(B, K))
+    mc = ClosedLoopMonteCarlo(h.ops, params(N))
+    kw = dict(seed=SEED, spheres=sph if K else None, obstacle_weight=W_OBS if K else 0.0, shift=None, latency_depth=depth,
+              wind={"rows": w, None: None, "shared": w[0].contiguous()}[wind])
+    return mc, (p0, v0, goal, cycles, substeps, SIM_DT, S, ITERS, SIGMA, LAM), kw
+
+
+def _host(h, out, depth):
+    res = {k: np.array(h.to_host(out[k])) for k in STATE_KEYS + PLAN_KEYS}
+    if depth > 0:
+        res.update({"latency_" + k: np.array(h.to_host(out["latency"][k])) for k in LATENCY_KEYS})
+    return res
+
+
+_chain = {}
+
+
+def chain(h, shape, depth, substeps, wind="rows", cycles=CYCLES, log=False):
+    """ClosedLoopMonteCarlo.run_mppi_edge for the configuration, as host arrays (computed once, never written).  With `log` also plan_last =
+    the last cycle's plan and visited (cycles * substeps, B, 3) = the position after every simulator step."""
+    key = (id(h.ops), np.dtype(h.dt).name, shape, depth, substeps, wind, cycles, log)
+    if key not in _chain:
+        mc, args, kw = _operands(h, shape, depth, substeps, wind, cycles)
+        out = mc.run_mppi_edge(*args, log=log, **kw)
+        assert out["clearance"] is None                                 # the chain measures no clearance: why the one launch exists
+        res = _host(h, out, depth)
+        if log:
+            assert len(out["logs"]) == cycles
+            res["plan_last"] = np.array(h.to_host(out["logs"][-1][0]["plan_last"]))
+            # log_state row s = the state BEFORE step s, and the planner's launch moves no drone: the positions after the steps are every row
+            # but the run's first, and the position the run leaves
+            rows = np.concatenate([h.to_host(flown["log_state"])[:, :, :3] for _, flown in out["logs"]], axis=0)
+            res["visited"] = np.concatenate([rows[1:], res["pos"][None]], axis=0)
+        else:
+            assert out["logs"] == []
+        for v in res.values():
+            v.setflags(write=False)
+        _chain[key] = res
+    return _chain[key]
+
+
+def check_not_vacuous(h, shape, substeps):
+    """Conditions on the CHAIN's results (never on the code under test) under which the byte comparisons say something: nothing blows up, every
+    drone gets its stale-state zero command with a buffer, the buffers fill and count, and the delay moves every drone by more than MOVES."""
+    runs = {d: chain(h, shape, d, substeps) for d in DEPTHS}
+    steps = CYCLES * substeps
+    for d, r in runs.items():
+        for key, v in r.items():
+            assert np.isfinite(v).all(), (d, key)
+        if d >= 1:
+            assert (r["zero_thrust_steps"] >= 1).all(), (d, r["zero_thrust_steps"])
+            assert (r["latency_state"][:, 2] == steps).all() and (r["latency_state"][:, 0] == min(d, steps)).all(), (d, r["latency_state"])
+        else:
+            assert not any(k.startswith("latency_") for k in r)
+    moved = float(np.abs(runs[5]["pos"].astype(np.float64) - runs[0]["pos"]).max(axis=1).min())
+    print(f"{shape} substeps={substeps} {np.dtype(h.dt).name}: zero-thrust steps "
+          + ", ".join(f"depth {d}: {int(r['zero_thrust_steps'].min())}..{int(r['zero_thrust_steps'].max())}" for d, r in runs.items())
+          + f"; least |pos(depth 5) - pos(depth 0)| of a drone {moved:.3g} m")
+    assert moved > MOVES, moved
+
+
+def check_equals_chain(h, shape, depth, substeps, wind="rows", last_plan=False):
+    """run_mppi_edge_fused gives the bytes of run_mppi_edge: the drones' state, the clocks, the onboard records, the counters, the nominal,
+    the last cost and every trace row and -- with a buffer -- the latency records and the whole ring; with `last_plan` also the last cycle's
+    plan, against the logged chain (which must itself fly the bytes of the unlogged one)."""
+    ref = chain(h, shape, depth, substeps, wind)
+    mc, args, kw = _operands(h, shape, depth, substeps, wind)
+    got = mc.run_mppi_edge_fused(*args, want_last_plan=last_plan, **kw)
+    assert got["logs"] == [] and got["latency"]["depth"] == depth and "controller_state" not in got
+    what = f"{shape} depth={depth} substeps={substeps} wind={wind}"
+    same_run(_host(h, got, depth), ref, what)
+    if shape[2]:
+        clr = h.to_host(got["clearance"])
+        assert clr.shape == (shape[1],) and np.isfinite(clr).all(), clr
+    else:
+        assert got["clearance"] is None
+    if not last_plan:
+        assert got["plan_last"] is None
+        return
+    logged = chain(h, shape, depth, substeps, wind, log=True)
+    same_run({k: logged[k] for k in ref}, ref, what + ": the logged chain against the unlogged")
+    same_bits(h.to_host(got["plan_last"]), logged["plan_last"], what + ": plan_last")
+
+
+def _fresh(h, shape, depth, lo=0, hi=None):
+    """Fresh operands of Ops.mppi_closed_loop_edge for drones [lo, hi) of the scene, as run_mppi_edge_fused makes them -> (the in / out
+    operands, the inputs)."""
+    N, B, K, S = shape
+    hi = B if hi is None else hi
+    n = hi - lo
+    p0, v0, goal, w, sph = scene(B, K)
+    prm = params(N)
+    ops, lib = h.ops, h.ops.lib
+    z = np.zeros((n, 3))
+    st = dict(onboard_state=ops.onboard_state(n), latency=ops.latency_buffer(n, depth, "f64" if h.dt == np.float64 else "f32"),
+              time=h.to_dev(np.zeros(n)), pos=h.prob(p0[lo:hi]), vel=h.prob(v0[lo:hi]), att=h.prob(z), omega=h.prob(z),
+              U=h.prob(np.tile([0.0, 0.0, prm.mass * prm.gravity], (n, N, 1))), zero_thrust_steps=h.to_dev(np.zeros(n, dtype=np.int32)),
+              clearance=h.prob(np.full(n, np.inf)) if K else None)
+    fixed = dict(prm=prm, op=lib.onboard_default_params(), sp=lib.simulator_default_params(), goal=h.prob(goal[lo:hi]), spheres=h.prob(sph) if K else None,
+                 wind=h.prob(w[lo:hi]), lo=lo, S=S, K=K, depth=depth)
+    return st, fixed
+
+
+def _launch(h, st, fx, cycles, substeps, cycle_base=0, shift=1, iter_base=5):
+    return h.ops.mppi_closed_loop_edge(fx["prm"], fx["op"], fx["sp"], st["onboard_state"], st["latency"], st["time"], st["pos"], st["vel"], st["att"],
+                                       st["omega"], fx["goal"], st["U"], cycles, substeps, SIM_DT, fx["S"], ITERS, SIGMA, LAM, seed=SEED,
+                                       cycle_base=cycle_base, shift=shift, iter_base=iter_base, index_base=fx["lo"], spheres=fx["spheres"],
+                                       obstacle_weight=W_OBS if fx["K"] else 0.0, wind=fx["wind"], want_plan=True, clearance=st["clearance"],
+                                       zero_thrust_steps=st["zero_thrust_steps"])
+
+
+def _state(h, st, depth, with_clearance=True):
+    """The in / out operands as host arrays, under the names _host gives them (+ clearance)."""
+    res = {k: np.array(h.to_host(st[k])) for k in STATE_KEYS + ("U",)}
+    if with_clearance and st["clearance"] is not None:
+        res["clearance"] = np.array(h.to_host(st["clearance"]))
+    if depth > 0:
+        res.update({"latency_" + k: np.array(h.to_host(st["latency"][k])) for k in LATENCY_KEYS})
+    return res
+
+
+def check_cycles_equal_calls(h, shape, depth, substeps):
+    """Ops.mppi_closed_loop_edge: one call of CYCLES cycles == CYCLES calls of one cycle with cycle_base = 0 .. CYCLES - 1 == calls of 1 + (CYCLES - 1)
+    cycles, on the same operands: every operand, the running clearance (passed back in, it continues), the cost, the last plan and every trace
+    row as bytes.  With the chain's shift and iter_base = 0 the one call is also the chain."""
+    one, fx = _fresh(h, shape, depth)
+    o1 = _launch(h, one, fx, CYCLES, substeps)
+    assert o1["U"] is one["U"] and (o1["clearance"] is one["clearance"]) and (one["clearance"] is None) == (shape[2] == 0)
+    whole = _state(h, one, depth)
+    for parts in ([1] * CYCLES, [1, CYCLES - 1]):
+        st, _ = _fresh(h, shape, depth)
+        outs, base = [], 0
+        for n in parts:
+            outs.append(_launch(h, st, fx, n, substeps, cycle_base=base))
+            base += n
+        what = f"{shape} depth={depth} substeps={substeps}: {' + '.join(map(str, parts))} cycles against {CYCLES}"
+        same_run(_state(h, st, depth), whole, what)
+        same_bits(h.to_host(outs[-1]["cost"]), h.to_host(o1["cost"]), what + ": cost")
+        same_bits(h.to_host(outs[-1]["plan_last"]), h.to_host(o1["plan_last"]), what + ": plan_last")
+        same_bits(np.concatenate([h.to_host(o["trace"]) for o in outs], axis=1), h.to_host(o1["trace"]), what + ": trace")
+    mc = ClosedLoopMonteCarlo(h.ops, fx["prm"])
+    st, _ = _fresh(h, shape, depth)
+    oc = _launch(h, st, fx, CYCLES, substeps, shift=mc.resolve_shift(substeps, SIM_DT), iter_base=0)
+    ref = chain(h, shape, depth, substeps)
+    got = dict(_state(h, st, depth, with_clearance=False), cost=h.to_host(oc["cost"]), trace=h.to_host(oc["trace"]))
+    same_run(got, ref, f"{shape} depth={depth} substeps={substeps}: Ops.mppi_closed_loop_edge against the chain")
+
+
+def check_slices(h, shape, depth, substeps):
+    """Drones [1, B - 1) with index_base = 1 and a ring of their own == those rows of the full batch and those columns of the full ring."""
+    N, B, K, S = shape
+    lo, hi = 1, B - 1
+    assert hi - lo >= 1
+    one, fx = _fresh(h, shape, depth)
+    o1 = _launch(h, one, fx, CYCLES, substeps)
+    whole = _state(h, one, depth)
+    part, fp = _fresh(h, shape, depth, lo, hi)
+    op = _launch(h, part, fp, CYCLES, substeps)
+    got = _state(h, part, depth)
+    assert sorted(got) == sorted(whole)
+    for k, v in got.items():
+        want = whole[k][..., lo:hi] if k in ("latency_ring", "latency_ring_time") else whole[k][lo:hi]
+        same_bits(v, want, f"{shape} depth={depth}: drones [{lo}, {hi}): {k}")
+    for k in ("cost", "trace", "plan_last"):
+        same_bits(h.to_host(op[k]), h.to_host(o1[k])[lo:hi], f"{shape} depth={depth}: drones [{lo}, {hi}): {k}")
+
+
+def check_long_act(h, shape, depth):
+    """An act phase of LONG_SUBSTEPS steps (two chunks of the kernel's clearance reduction) gives the chain's bytes; first, on the chain alone:
+    the run stays finite and fills and counts its buffer."""
+    ref = chain(h, shape, depth, LONG_SUBSTEPS, cycles=LONG_CYCLES)
+    steps = LONG_CYCLES * LONG_SUBSTEPS
+    for key, v in ref.items():
+        assert np.isfinite(v).all(), (depth, key)
+    assert (ref["latency_state"][:, 2] == steps).all() and (ref["latency_state"][:, 0] == min(depth, steps)).all(), ref["latency_state"]
+    assert (ref["zero_thrust_steps"] >= 1).all(), ref["zero_thrust_steps"]
+    mc, args, kw = _operands(h, shape, depth, LONG_SUBSTEPS, cycles=LONG_CYCLES)
+    got = mc.run_mppi_edge_fused(*args, **kw)
+    same_run(_host(h, got, depth), ref, f"{shape} depth={depth}: {LONG_CYCLES} x {LONG_SUBSTEPS} steps")
+    if shape[2]:
+        check_clearance(h, shape, depth, LONG_SUBSTEPS, cycles=LONG_CYCLES)
+
+
+def check_clearance(h, shape, depth, substeps, cycles=CYCLES):
+    """The clearance of the one launch against the positions the logged chain visited: the running minimum of |pos - c_j| - r_j over every
+    position a simulator step left, in float64 NumPy, within 16 eps_R max(|pos - c_j| + r_j) -- bound and argument of
+    mppi_closed_loop_staged_checks.check_clearance: the two evaluations differ only in the rounding and contraction of one three-term sum of
+    squares, a square root and a subtraction, each a few units of roundoff in R, and min is 1-Lipschitz.  Finite for every drone."""
+    N, B, K, S = shape
+    assert K > 0
+    ref = chain(h, shape, depth, substeps, cycles=cycles, log=True)
+    mc, args, kw = _operands(h, shape, depth, substeps, cycles=cycles)
+    fused = mc.run_mppi_edge_fused(*args, **kw)
+    same_bits(h.to_host(fused["pos"]), ref["pos"], "the logged flight ends where the one launch ends")
+    visited = ref["visited"].astype(np.float64)
+    assert visited.shape == (cycles * substeps, B, 3)
+    sph = scene(B, K)[4].astype(h.dt).astype(np.float64)
+    dist = np.linalg.norm(visited[:, :, None, :] - sph[None, None, :, :3], axis=-1)  # (steps, B, K)
+    want = (dist - sph[:, 3]).min(axis=(0, 2))
+    bound = 16 * float(np.finfo(h.dt).eps) * float((dist + sph[:, 3]).max())
+    clr = h.to_host(fused["clearance"]).astype(np.float64)
+    assert clr.shape == (B,) and np.isfinite(clr).all(), clr
+    err = float(np.abs(clr - want).max())
+    print(f"{shape} depth={depth} substeps={substeps} {np.dtype(h.dt).name}: clearance error {err:.3e} (bound {bound:.3e}), clearance {want.min():.4f} .. {want.max():.4f} m")
+    assert err <= bound, (err, bound)
+
+
+def check_planner_inside(h, shape, depth=2):
+    """substeps = 0: U, cost, trace and plan_last are those of se3mpc_mppi_closed_loop_* with substeps = 0, as bytes, and no state, record,
+    ring, clock or counter is touched (they hold noise that must come back byte for byte)."""
+    N, B, K, S = shape
+    ops = h.ops
+    rng = np.random.default_rng(5)
+    st, fx = _fresh(h, shape, depth)
+    noise = dict(onboard_state=rng.normal(0, 1, (B, 14)), time=rng.uniform(0, 1, B))
+    st["onboard_state"], st["time"] = h.to_dev(noise["onboard_state"]), h.to_dev(noise["time"])
+    st["latency"] = dict(depth=depth, ring=h.prob(rng.normal(0, 1, (depth, 12, B))), ring_time=h.to_dev(rng.uniform(0, 1, (depth, B))),
+                         state=h.to_dev(np.tile([1.0, 0.0, 7.0, 0.25], (B, 1))))
+    st["att"], st["omega"] = h.prob(rng.normal(0, 0.1, (B, 3))), h.prob(rng.normal(0, 0.1, (B, 3)))
+    st["zero_thrust_steps"] = h.to_dev(np.arange(B, dtype=np.int32) + 3)
+    before = _state(h, st, depth)
+    got = _launch(h, st, fx, CYCLES, 0)
+    after = _state(h, st, depth)
+    for k in before:
+        if k != "U":
+            same_bits(after[k], before[k], f"{shape} substeps=0: {k} untouched")
+    if K:
+        assert np.isinf(after["clearance"]).all(), "no step, no clearance"
+    ref_st, _ = _fresh(h, shape, 0)
+    cp = ops.lib.controller_default_params()
+    ref = ops.mppi_closed_loop(fx["prm"], cp, fx["sp"], ops.controller_state(cp, B), ref_st["time"], ref_st["pos"], ref_st["vel"], ref_st["att"],
+                               ref_st["omega"], fx["goal"], ref_st["U"], CYCLES, 0, SIM_DT, S, ITERS, SIGMA, LAM, seed=SEED, cycle_base=0, shift=1,
+                               iter_base=5, index_base=0, spheres=fx["spheres"], obstacle_weight=W_OBS if K else 0.0, wind=fx["wind"], want_plan=True)
+    for k in ("U", "cost", "trace", "plan_last"):
+        same_bits(h.to_host(got[k]), h.to_host(ref[k]), f"{shape} substeps=0: {k} against se3mpc_mppi_closed_loop")
+
+
+def check_argument_rules(h):
+    """Every rule of include/se3mpc.h returns its code with all operands untouched; B = 0 and cycles = 0 are no-ops; depth = 0 is accepted with
+    its three operands NULL."""
+    import torch
+    ops, lib = h.ops, h.ops.lib
+    suf = "f32" if h.dt == np.float32 else "f64"
+    NULL, SHAPE, PARAM = -1, -3, -4                                             # SE3MPC_ERR_NULL, _SHAPE, _PARAM (include/se3mpc.h)
+    B, N, K, depth = 3, 6, 2, 2
+    prm, op, sp = params(N), lib.onboard_default_params(), lib.simulator_default_params()
+    assert prm.has_goal
+    rng = np.random.default_rng(3)
+    noise = lambda *s: rng.uniform(0.5, 1.5, s)
+    host = dict(time=noise(B), st=noise(B, 14), lst=np.tile([1.0, 0.0, 4.0, 0.5], (B, 1)), rt=noise(depth, B), zeros=np.arange(B, dtype=np.int32) + 1)
+    typed = dict(ring=noise(depth, 12, B), pos=noise(B, 3), vel=noise(B, 3), att=noise(B, 3) * 0.1, omega=noise(B, 3) * 0.1, goal=noise(B, 3), wind=noise(B, 3),
+                 U=np.tile([0.0, 0.0, prm.mass * prm.gravity], (B, N, 1)), cost=noise(B), trace=noise(B, 1, 1), plan=noise(B, 3, N, 3), clr=np.full(B, np.inf),
+                 sph=np.array([[5.0, 5.0, 5.0, 0.5], [-5.0, 5.0, 5.0, 0.5]]))
+    dev = {k: h.to_dev(v) for k, v in host.items()}
+    dev.update({k: h.prob(v) for k, v in typed.items()})
+    ptr = ops.be.ptr
+    default = dict(prm=prm, op=op, sp=sp, B=B, cycles=1, substeps=2, sim_dt=0.01, base=0, shift=1, S=64, iters=1, sigma=1.0, lam=1.0, goal=ptr(dev["goal"]),
+                   sph=ptr(dev["sph"]), K=K, w_obs=1.0, wind=0, wstride=0, time=ptr(dev["time"]), pos=ptr(dev["pos"]), vel=ptr(dev["vel"]), att=ptr(dev["att"]),
+                   omega=ptr(dev["omega"]), st=ptr(dev["st"]), depth=depth, ring=ptr(dev["ring"]), rt=ptr(dev["rt"]), lst=ptr(dev["lst"]), zeros=ptr(dev["zeros"]),
+                   U=ptr(dev["U"]), cost=ptr(dev["cost"]), trace=ptr(dev["trace"]), plan=ptr(dev["plan"]), clr=ptr(dev["clr"]))
+
+    def status(**kw):
+        a = dict(default, **kw)
+        assert not set(kw) - set(default)
+        return lib.loop_status("mppi_closed_loop_edge", suf, a["prm"], a["op"], a["sp"], a["B"], a["cycles"], a["substeps"], a["sim_dt"], a["base"], a["shift"],
+                               a["S"], a["iters"], a["sigma"], a["lam"], 0, 0, 0, a["goal"], a["sph"], a["K"], a["w_obs"], a["wind"], a["wstride"], a["time"],
+                               a["pos"], a["vel"], a["att"], a["omega"], a["st"], a["depth"], a["ring"], a["rt"], a["lst"], a["zeros"], a["U"], a["cost"],
+                               a["trace"], a["plan"], a["clr"], ops.be.stream())
+
+    def broken(make, **fields):
+        p = make()
+        for k, v in fields.items():
+            setattr(p, k, v)
+        return p
+
+    nan, inf = float("nan"), float("inf")
+    rejected = [
+        (NULL, dict(prm=None)), (NULL, dict(op=None)), (NULL, dict(sp=None)),
+        (NULL, dict(time=0)), (NULL, dict(pos=0)), (NULL, dict(vel=0)), (NULL, dict(att=0)), (NULL, dict(omega=0)), (NULL, dict(st=0)), (NULL, dict(U=0)),
+        (NULL, dict(cost=0)), (NULL, dict(goal=0)), (NULL, dict(sph=0)), (NULL, dict(ring=0)), (NULL, dict(rt=0)), (NULL, dict(lst=0)),
+        (PARAM, dict(prm=Params.reference_defaults(horizon=N, dt=PLAN_DT, mass=nan))), (PARAM, dict(op=broken(lib.onboard_default_params, g=inf))),
+        (PARAM, dict(op=broken(lib.onboard_default_params, mass=0.0))), (PARAM, dict(sp=broken(lib.simulator_default_params, mass=-1.0))),
+        (PARAM, dict(sim_dt=nan)), (PARAM, dict(sim_dt=inf)),
+        (SHAPE, dict(B=-1)), (SHAPE, dict(cycles=-1)), (SHAPE, dict(substeps=-1)), (SHAPE, dict(shift=-1)), (SHAPE, dict(shift=N + 1)),
+        (SHAPE, dict(depth=-1)), (SHAPE, dict(depth=1001)),
+        (SHAPE, dict(wind=ptr(dev["wind"]), wstride=1)), (SHAPE, dict(wind=ptr(dev["wind"]), wstride=2)), (SHAPE, dict(wind=ptr(dev["wind"]), wstride=-3)),
+        (SHAPE, dict(base=2 ** 30, cycles=2 ** 30 - 1, substeps=2)), (SHAPE, dict(base=0, cycles=2 ** 16, substeps=2 ** 15)),
+        (SHAPE, dict(base=2 ** 32 - 1, cycles=1, substeps=1)),
+        # the planner's own (check_mppi_args)
+        (SHAPE, dict(S=0)), (SHAPE, dict(S=63)), (SHAPE, dict(S=96)), (SHAPE, dict(S=65536 + 64)), (SHAPE, dict(iters=-1)), (SHAPE, dict(K=-1)), (SHAPE, dict(K=257)),
+        (PARAM, dict(lam=0.0)), (PARAM, dict(lam=nan)), (PARAM, dict(lam=inf)), (PARAM, dict(sigma=-0.5)), (PARAM, dict(sigma=nan)), (PARAM, dict(w_obs=-1.0)),
+        (lib.check_params(Params.reference_defaults(horizon=65)), dict(prm=Params.reference_defaults(horizon=65))),
+    ]
+    for code, kw in rejected:
+        got = status(**kw)
+        assert code < 0 and got == code, (code, kw, got)
+        assert lib.last_error(), f"{kw}: se3mpc_last_error not set"
+    # no-ops, with nothing else there
+    assert status(B=0, time=0, pos=0, vel=0, att=0, omega=0, st=0, U=0, cost=0, goal=0, sph=0, ring=0, rt=0, lst=0, zeros=0, trace=0, plan=0, clr=0) == 0
+    assert status(cycles=0, time=0, pos=0, vel=0, att=0, omega=0, st=0, U=0, cost=0, goal=0, sph=0, ring=0, rt=0, lst=0, zeros=0, trace=0, plan=0, clr=0) == 0
+    assert status(cycles=0, base=2 ** 32 - 1, substeps=0) == 0
+    if hasattr(torch, "cuda") and torch.cuda.is_available():
+        torch.cuda.synchronize()
+    for k, v in {**host, **typed}.items():
+        want = v if k in host else np.asarray(v, float).astype(h.dt)
+        same_bits(np.asarray(h.to_host(dev[k])), np.ascontiguousarray(want), f"a rejected call or a no-op wrote {k}")
+    # accepted: no buffer with its three operands NULL; the optional outputs absent; wind strides 0 and 3; the shifts at both ends; no steps
+    assert status(depth=0, ring=0, rt=0, lst=0, zeros=0) == 0
+    assert status(trace=0, plan=0, clr=0, zeros=0) == 0 and status(K=0, sph=0) == 0
+    assert status(wind=ptr(dev["wind"]), wstride=0) == 0 and status(wind=ptr(dev["wind"]), wstride=3) == 0
+    assert status(shift=0) == 0 and status(shift=N) == 0 and status(substeps=0) == 0 and status() == 0
+    if hasattr(torch, "cuda") and torch.cuda.is_available():
+        torch.cuda.synchronize()
+    assert (np.asarray(h.to_host(dev["zeros"])) >= host["zeros"]).all() and np.isfinite(np.asarray(h.to_host(dev["pos"]))).all()
+    del dev

@@ -97,6 +97,15 @@ class VoxelMapDesc(C.Structure):
                 ("reserved", C.c_int32), ("resolution", C.c_double), ("prior", C.c_double)]
 
 
+class UFieldDesc(C.Structure):
+    """struct se3mpc_ufield: the caller-owned dense grids of the device uncertainty field (device addresses)."""
+    _fields_ = [("uncertainty", C.c_void_p), ("observation_count", C.c_void_p), ("n", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("origin", C.c_double * 3), ("resolution", C.c_double)]
+
+
+assert C.sizeof(UFieldDesc) == 64      # static_assert in csrc/uncertainty_field.hip
+
+
 class ControllerParams(C.Structure):
     """struct se3mpc_controller_params == GeometricControllerConfig after its tuning profile
     (src/dart_planner/control/geometric_controller.py:26-77, :140-158), unit-stripped."""
@@ -318,6 +327,18 @@ _VOXEL_PLAIN_API = {
     "se3mpc_voxel_export": (C.c_int, [_VP, _P, _P, _P, _P, _P]),
     "se3mpc_voxel_local_workspace": (C.c_int, [_I]),
 }
+# uncertainty field: se3mpc_ufield_<name>(const se3mpc_ufield*, ...); workspace and targets take no descriptor
+_UP = C.POINTER(UFieldDesc)
+_UFIELD_API = {
+    "se3mpc_ufield_workspace": (C.c_longlong, [_I, _I, _I, _I]),
+    "se3mpc_ufield_fill": (C.c_int, [_UP, _P]),
+    "se3mpc_ufield_stamp": (C.c_int, [_UP, _P, _P, _P, _P, _I, _P]),
+    "se3mpc_ufield_update_points": (C.c_int, [_UP, _P, _P, _P, _I, _D, _P, _P, C.c_longlong, _P]),
+    "se3mpc_ufield_query": (C.c_int, [_UP, _P, _I, _P, _P]),
+    "se3mpc_ufield_statistics": (C.c_int, [_UP, _D, _P, _P, _P, C.c_longlong, _P]),
+    "se3mpc_ufield_regions": (C.c_int, [_UP, _D, _D, _I, _P, _P, _P, _P, _P, C.c_longlong, _P]),
+    "se3mpc_ufield_targets": (C.c_int, [_P, _P, _I, C.POINTER(C.c_double * 3), _P, _P, _P]),
+}
 _CP = C.POINTER(ControllerParams)
 _SP = C.POINTER(SimulatorParams)
 _MP = C.POINTER(SmootherParams)
@@ -395,6 +416,7 @@ def exported_symbols() -> list:
     names += list(_VOXEL_PLAIN_API)
     for base in _VOXEL_TYPED_API:
         names += [f"se3mpc_voxel_{base}_f32", f"se3mpc_voxel_{base}_f64"]
+    names += list(_UFIELD_API)
     return names
 
 
@@ -436,6 +458,9 @@ class Library:
                 fn = getattr(self._dll, f"se3mpc_voxel_{base}_{suf}")
                 fn.restype = C.c_int
                 fn.argtypes = [_VP] + args
+        for name, (res, args) in _UFIELD_API.items():
+            fn = getattr(self._dll, name)
+            fn.restype, fn.argtypes = res, args
         if self._dll.se3mpc_abi_version() != 1:
             raise Se3mpcLibraryError(f"{self.path}: ABI version {self._dll.se3mpc_abi_version()} != 1")
 
@@ -564,6 +589,27 @@ class Library:
 
     def voxel_update_row_words(self, M: int, max_len: int) -> int:
         return self._dll.se3mpc_voxel_update_row_words(M, max_len)
+
+    # -- uncertainty field --------------------------------------------------------------------
+    def ufield(self, name: str, desc: UFieldDesc, *args) -> None:
+        """Call se3mpc_ufield_<name>(&desc, *args) (name = 'fill', 'stamp', 'update_points', 'query', 'statistics', 'regions')."""
+        self._check(f"se3mpc_ufield_{name}", getattr(self._dll, f"se3mpc_ufield_{name}")(C.byref(desc), *args))
+
+    def ufield_status(self, name: str, desc: Optional[UFieldDesc], *args) -> int:
+        return getattr(self._dll, f"se3mpc_ufield_{name}")(C.byref(desc) if desc is not None else None, *args)
+
+    def ufield_workspace(self, nx: int, ny: int, nz: int, max_regions: int) -> int:
+        return self._dll.se3mpc_ufield_workspace(nx, ny, nz, max_regions)
+
+    @staticmethod
+    def _position(position):
+        return None if position is None else (C.c_double * 3)(*[float(v) for v in position])
+
+    def ufield_targets(self, regions: int, counts: int, num_targets: int, position, targets: int, n_out: int, stream: int) -> None:
+        self._check("se3mpc_ufield_targets", self._dll.se3mpc_ufield_targets(regions, counts, num_targets, self._position(position), targets, n_out, stream))
+
+    def ufield_targets_status(self, regions: int, counts: int, num_targets: int, position, targets: int, n_out: int, stream: int) -> int:
+        return self._dll.se3mpc_ufield_targets(regions, counts, num_targets, self._position(position), targets, n_out, stream)
 
     def _check(self, name: str, rc: int) -> None:
         if rc != 0:

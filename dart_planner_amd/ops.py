@@ -19,7 +19,7 @@ import numpy as np
 
 from .capi import (CONTROLLER_STATE_WORDS, LATENCY_MAX_DEPTH, LATENCY_STATE_WORDS, MIXER_STATE_WORDS, ONBOARD_STATE_WORDS, SMOOTHER_STATE_WORDS,
                    SE3MPC_MAX_SPHERES, ControllerParams, Library, MixerParams, OnboardParams, Params, SimulatorParams, SmootherParams, SolveInfo,
-                   get_library)
+                   UFieldDesc, get_library)
 
 INFO_DTYPE = np.dtype([("fun", "<f8"), ("nit", "<i4"), ("nfev", "<i4"), ("status", "<i4"), ("task", "<i4")])
 assert INFO_DTYPE.itemsize == 24
@@ -1276,6 +1276,114 @@ class Ops:
                            *[self.be.ptr(logs.get(k)) for k in ("log_state", "log_cmd", "log_time", "log_target", "log_pwm", "log_wrench")],
                            self.be.stream())
         return logs
+
+    # ------------------------------------------------------------------ uncertainty field (mission layer, dense float64 grids)
+    def _f64(self, a, shape, name):
+        self.be.check(a, name)
+        if self.be.suffix(a) != "f64" or tuple(a.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected float64 {tuple(shape)}, got {tuple(a.shape)}")
+        return a
+
+    def _i32(self, a, min_words, name):
+        self.be.check(a, name)
+        if a.ndim != 1 or not str(a.dtype).endswith("int32"):
+            raise ValueError(f"{name}: expected a flat int32 array, got {a.dtype} {tuple(a.shape)}")
+        if a.shape[0] < min_words:
+            raise ValueError(f"{name}: {a.shape[0]} words, {min_words} needed")
+        return a
+
+    def ufield_desc(self, uncertainty, observation_count, origin, resolution: float) -> UFieldDesc:
+        """The descriptor of a field whose two float64 grids (n0, n1, n2) live on the backend; origin = scene_bounds[0]."""
+        self.be.check(uncertainty, "uncertainty")
+        if uncertainty.ndim != 3:
+            raise ValueError(f"uncertainty: expected a 3-D grid, got {tuple(uncertainty.shape)}")
+        n = tuple(int(x) for x in uncertainty.shape)
+        self._f64(uncertainty, n, "uncertainty")
+        self._f64(observation_count, n, "observation_count")
+        return UFieldDesc(uncertainty=self.be.ptr(uncertainty), observation_count=self.be.ptr(observation_count), n=(_C.c_int32 * 3)(*n), reserved=0,
+                          origin=(_C.c_double * 3)(*[float(v) for v in origin]), resolution=float(resolution))
+
+    def ufield_workspace(self, grid_size, max_regions: int):
+        """Zeroed int32 scratch that every ufield_* call accepts for this grid and up to max_regions rows."""
+        words = self.lib.ufield_workspace(int(grid_size[0]), int(grid_size[1]), int(grid_size[2]), int(max_regions))
+        if words < 0:
+            raise ValueError(f"ufield_workspace: grid {tuple(grid_size)} / max_regions {max_regions} refused")
+        ws = self.be.empty((words,), "i32")
+        ws[...] = 0
+        return ws
+
+    def ufield_fill(self, desc: UFieldDesc) -> None:
+        self.lib.ufield("fill", desc, self.be.stream())
+
+    def ufield_stamp(self, desc: UFieldDesc, centres, radius, radius_voxels, factor) -> None:
+        """S stamps (reduce_uncertainty_around_position) in one launch, in index order: centres (S, 3), radius (S,), radius_voxels int32 (S,) =
+        int(radius / resolution) in the caller's float64, factor (S,)."""
+        S = centres.shape[0]
+        self._f64(centres, (S, 3), "centres")
+        self._f64(radius, (S,), "radius")
+        self._f64(factor, (S,), "factor")
+        self._i32(radius_voxels, S, "radius_voxels")
+        self.lib.ufield("stamp", desc, self.be.ptr(centres), self.be.ptr(radius), self.be.ptr(radius_voxels), self.be.ptr(factor), S, self.be.stream())
+
+    def ufield_update_points(self, desc: UFieldDesc, positions, uncertainties, weights=None, alpha: float = 0.1, workspace=None) -> None:
+        """update_uncertainty_field: positions (N, 3), uncertainties (N,), weights (N,) or None; same-voxel points in input order."""
+        N = positions.shape[0]
+        self._f64(positions, (N, 3), "positions")
+        self._f64(uncertainties, (N,), "uncertainties")
+        if weights is not None:
+            self._f64(weights, (N,), "weights")
+        if workspace is None:
+            workspace = self.ufield_workspace(tuple(desc.n), 1)
+        self._i32(workspace, 0, "workspace")
+        keys = self.be.empty((max(N, 1),), "i32")
+        self.lib.ufield("update_points", desc, self.be.ptr(positions), self.be.ptr(uncertainties), self.be.ptr(weights), N, float(alpha),
+                        self.be.ptr(keys), self.be.ptr(workspace), workspace.shape[0], self.be.stream())
+
+    def ufield_query(self, desc: UFieldDesc, positions):
+        """get_uncertainty_at_position for positions (B, 3) -> (B,), 1.0 outside the bounds."""
+        B = positions.shape[0]
+        self._f64(positions, (B, 3), "positions")
+        out = self.be.empty((B,), "f64")
+        self.lib.ufield("query", desc, self.be.ptr(positions), B, self.be.ptr(out), self.be.stream())
+        return out
+
+    def ufield_statistics(self, desc: UFieldDesc, threshold: float, workspace=None):
+        """dict(counts int32 (2,) = observed voxels, voxels above the threshold; values (3,) = sum, min, max of the uncertainty)."""
+        if workspace is None:
+            workspace = self.ufield_workspace(tuple(desc.n), 1)
+        self._i32(workspace, 0, "workspace")
+        out = dict(counts=self.be.empty((2,), "i32"), values=self.be.empty((3,), "f64"))
+        self.lib.ufield("statistics", desc, float(threshold), self.be.ptr(out["counts"]), self.be.ptr(out["values"]), self.be.ptr(workspace),
+                        workspace.shape[0], self.be.stream())
+        return out
+
+    def ufield_regions(self, desc: UFieldDesc, threshold: float, min_volume: float, max_regions: int, workspace=None, labels=None):
+        """identify_high_uncertainty_regions: dict(labels int32 (n0, n1, n2), regions (max_regions, 12), roots int32 (max_regions,), counts int32
+        (2,) = rows written, regions that qualify).  Rows beyond counts[0] are not written."""
+        n = tuple(desc.n)
+        if workspace is None:
+            workspace = self.ufield_workspace(n, max_regions)
+        self._i32(workspace, 0, "workspace")
+        if labels is None:
+            labels = self.be.empty(n, "i32")
+        self.be.check(labels, "labels")
+        if tuple(labels.shape) != n:
+            raise ValueError(f"labels: expected int32 {n}, got {tuple(labels.shape)}")
+        rows = max(int(max_regions), 1)
+        out = dict(labels=labels, regions=self.be.empty((rows, 12), "f64"), roots=self.be.empty((rows,), "i32"), counts=self.be.empty((2,), "i32"))
+        self.lib.ufield("regions", desc, float(threshold), float(min_volume), int(max_regions), self.be.ptr(labels), self.be.ptr(out["regions"]),
+                        self.be.ptr(out["roots"]), self.be.ptr(out["counts"]), self.be.ptr(workspace), workspace.shape[0], self.be.stream())
+        return out
+
+    def ufield_targets(self, regions, counts, num_targets: int, position=None):
+        """The target list of get_exploration_targets from the rows and counts of ufield_regions: (targets (num_targets, 3), n int32 (1,))."""
+        self.be.check(regions, "regions")
+        self.be.check(counts, "counts")
+        targets = self.be.empty((max(int(num_targets), 1), 3), "f64")
+        n_out = self.be.empty((1,), "i32")
+        self.lib.ufield_targets(self.be.ptr(regions), self.be.ptr(counts), int(num_targets), position, self.be.ptr(targets), self.be.ptr(n_out),
+                                self.be.stream())
+        return targets, n_out
 
     # ------------------------------------------------------------------ problem layout
     def solve(self, params: Params, p0, v0, goal, x0=None, want_trajectory=True, out=None):

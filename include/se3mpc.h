@@ -473,6 +473,64 @@ int se3mpc_voxel_local_spheres_f64(const se3mpc_voxel_map* m, const double* cent
                                    int target, double radius, double* spheres, int cap, int32_t* count,
                                    int32_t* workspace, void* stream);
 
+/* ------------------------------------------------------------------ uncertainty field (mission layer)
+ * Device-resident counterpart of UncertaintyField (src/dart_planner/neural_scene/uncertainty_field.py, "field.py" below): the
+ * two dense float64 grids of field.py:58-59 in HBM, owned by the caller, C order with k fastest.  n = ceil((max - min) /
+ * resolution) is computed by the caller as field.py:53-55 does.  Float64 only: every number is the reference's.  All entry
+ * points are stream-ordered and allocate nothing.
+ *
+ * Argument rules of this section: a NULL descriptor, grid or required operand: SE3MPC_ERR_NULL; a grid size < 1, more than 2^30
+ * voxels, a count (S, N, B) outside [0, 2^30], max_regions outside [1, 2^30], num_targets outside [0, 1024]: SE3MPC_ERR_SHAPE; a resolution that is not finite
+ * and positive, a non-finite origin or alpha: SE3MPC_ERR_PARAM; a workspace of fewer words than needed or not 8-byte aligned:
+ * SE3MPC_ERR_WORKSPACE.  A count of 0 is a no-op.  Every rejected call sets se3mpc_last_error and launches nothing. */
+typedef struct se3mpc_ufield {
+  double* uncertainty;        /* [n0][n1][n2] uncertainty_grid   (field.py:58)                  */
+  double* observation_count;  /* [n0][n1][n2] observation_count  (field.py:59)                  */
+  int32_t n[3];               /* grid_size                       (field.py:53-55)               */
+  int32_t reserved;
+  double origin[3];           /* scene_bounds[0]                                                */
+  double resolution;          /* voxel edge in metres                                           */
+} se3mpc_ufield;
+
+/* Words of int32 workspace that every entry point of this section accepts for a grid of nx * ny * nz voxels and max_regions
+ * rows (7 words per voxel, 2 per 1024 voxels and 27 per row, at least 2048); negative: SE3MPC_ERR_SHAPE.  The workspace may be
+ * dirty: every word a call reads was written by that call. */
+long long se3mpc_ufield_workspace(int nx, int ny, int nz, int max_regions);
+/* uncertainty = 1, observation_count = 0 (field.py:58-59). */
+int se3mpc_ufield_fill(const se3mpc_ufield* f, void* stream);
+/* reduce_uncertainty_around_position (field.py:221-260) S times in ONE launch, in index order: centres [S][3], radius [S],
+ * radius_voxels [S] = int(radius / resolution) as the caller's float64 gives it (field.py:234), factor [S] = reduction_factor.
+ * The bytes of the two grids equal those of S sequential calls. */
+int se3mpc_ufield_stamp(const se3mpc_ufield* f, const double* centres, const double* radius, const int32_t* radius_voxels,
+                        const double* factor, int S, void* stream);
+/* update_uncertainty_field (field.py:90-108): positions [N][3], uncertainty [N], weights [N] or NULL (1.0), alpha = 0.1 in
+ * the reference.  Points outside the grid are ignored; points of one voxel are applied in input order.  keys: device
+ * int32[N] scratch; workspace: 2 words per voxel. */
+int se3mpc_ufield_update_points(const se3mpc_ufield* f, const double* positions, const double* uncertainty,
+                                const double* weights, int N, double alpha, int32_t* keys, int32_t* workspace,
+                                long long workspace_words, void* stream);
+/* get_uncertainty_at_position (field.py:110-125) for B positions [B][3]: out [B], 1.0 outside the bounds. */
+int se3mpc_ufield_query(const se3mpc_ufield* f, const double* positions, int B, double* out, void* stream);
+/* The sums of get_statistics (field.py:262-289): counts int32[2] = {voxels with observation_count > 0, voxels with
+ * uncertainty > threshold}, values [3] = {sum, min, max of the uncertainty}.  A fold in a fixed order: two runs give the
+ * same bytes.  workspace: 2048 words. */
+int se3mpc_ufield_statistics(const se3mpc_ufield* f, double threshold, int32_t* counts, double* values, int32_t* workspace,
+                             long long workspace_words, void* stream);
+/* identify_high_uncertainty_regions (field.py:154-182, :308-405): the 6-connected components of uncertainty > threshold.
+ * labels int32 [n0][n1][n2]: the smallest raster index of the voxel's component, -1 outside the mask.  Components with
+ * voxels * resolution^3 >= min_volume are kept in ascending order of that index (the reference's discovery order), at most
+ * max_regions of them; counts int32[2] = {rows written, regions that qualify}.  regions [max_regions][12] = centre 3, min
+ * 3, max 3, uncertainty_value, volume, priority, sorted by priority descending as Python's stable sort does; region_roots
+ * int32[max_regions] or NULL: the label of each row.  Eight launches, no host round trip; two runs give the same bytes. */
+int se3mpc_ufield_regions(const se3mpc_ufield* f, double threshold, double min_volume, int max_regions, int32_t* labels,
+                          double* regions, int32_t* region_roots, int32_t* counts, int32_t* workspace,
+                          long long workspace_words, void* stream);
+/* The target list of get_exploration_targets (field.py:204-219) from the rows and counts of se3mpc_ufield_regions (device):
+ * the centres of the first min(num_targets, counts[0]) rows with z = max(z, 2.0); position: HOST pointer to 3 doubles or
+ * NULL; with it the targets are stably sorted by distance.  targets [num_targets][3], n_out int32[1]. */
+int se3mpc_ufield_targets(const double* regions, const int32_t* counts, int num_targets, const double* position,
+                          double* targets, int32_t* n_out, void* stream);
+
 /* ------------------------------------------------------------------ consumer side of the contract
  * Plan sample -> geometric controller -> simulator, one drone per lane.  Reference ("controller.py" =
  * src/dart_planner/control/geometric_controller.py, "onboard.py" = src/dart_planner/control/onboard_controller.py,

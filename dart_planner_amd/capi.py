@@ -306,6 +306,7 @@ _TYPED_API = {
     "transpose": (False, [_I, _I, _P, _I, _P, _I, _P]),
     "population_sums": (False, [_I, _I, _I, _P, _P, _D, _P, _D, _P, _P, _P]),
     "mppi": (True, [_I, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _P]),
+    "mppi_moving": (True, [_I, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _D, _I, _D, _P, _P, _P, _P]),
     "mppi_split": (True, [_I, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _I, _P, C.c_size_t,
                           _P]),
     "mppi_samples": (True, [_I, _I, _I, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _P, _P, _P]),
@@ -374,6 +375,8 @@ _LOOP_TYPED_API = {
     "monte_carlo_edge": [_PP, _OP, _SP, _I, _I, _I, _D, _I, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mppi_closed_loop": [_PP, _CP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _D, _P, _LL,
                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mppi_closed_loop_moving": [_PP, _CP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, _D, _I,
+                                _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mppi_closed_loop_staged": [_PP, _CP, _SP, _MP, _XP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I,
                                 _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P],
     "mppi_closed_loop_edge": [_PP, _OP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _D, _P,

@@ -49,6 +49,11 @@ class ClosedLoopMonteCarlo:
                              "use run / run_mppi with mixer=")
 
     @staticmethod
+    def _no_moving(sphere_velocities, what: str) -> None:
+        if sphere_velocities is not None:
+            raise ValueError(f"{what}: moving spheres are not built for this form (DESIGN.md 5.8f): use run_mppi or run_mppi_fused")
+
+    @staticmethod
     def _mixer_option(mixer, motor_health) -> None:
         if motor_health is not None and mixer is None:
             raise ValueError("motor_health scales what the mixer's motors deliver: it needs mixer=")
@@ -250,7 +255,8 @@ class ClosedLoopMonteCarlo:
 
     def run_mppi(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
                  seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None, nominal=None,
-                 log: bool = False, smoother: Optional[SmootherParams] = None, mixer: Optional[MixerParams] = None, motor_health=None):
+                 log: bool = False, smoother: Optional[SmootherParams] = None, mixer: Optional[MixerParams] = None, motor_health=None,
+                 sphere_velocities=None, sphere_t0: float = 0.0):
         """The receding-horizon Monte-Carlo with MPPI as the planner (``se3mpc_mppi_closed_loop_*``), one call per planning cycle: each
         cycle runs `iters` MPPI iterations of `n_samples` samples from the drone's own state on its nominal thrust sequence (hover, or
         `nominal` (B, N, 3)), hands the plan to the controller on the chip, takes `substeps` control + simulator steps and moves the
@@ -264,7 +270,11 @@ class ClosedLoopMonteCarlo:
         (``se3mpc_mppi_closed_loop_*`` with no simulator steps), update_trajectory against the previous cycle's plan and `substeps` steps of
         ``se3mpc_closed_loop_smoothed_*``; clearance is None (only the fused act phase measures it), smoother_state (B, 25) is added.
         mixer, motor_health: as in :meth:`run`; the act phase is then ``se3mpc_closed_loop_actuated_*`` on the handed-over plan, with or
-        without the smoother (clearance None likewise), and mixer_state (B, 5) is added."""
+        without the smoother (clearance None likewise), and mixer_state (B, 5) is added.
+        sphere_velocities: None, or (K, 3) rows (vx, vy, vz): the spheres move with constant velocity from the centres the table holds
+        `sphere_t0` seconds before the run starts (``se3mpc_mppi_closed_loop_moving_*``): every plan step is penalised and
+        every simulator step's clearance measured against the centres at that step's time.  With a smoother or a mixer the planner-only
+        call gets the velocities and the time of its cycle's start; clearance stays None."""
         import torch
         ops, prm = self.ops, self.params
         B, N = p0.shape[0], prm.horizon
@@ -281,7 +291,8 @@ class ClosedLoopMonteCarlo:
             # without a smoother the kernel flies the act phase itself; with one it only plans, and every cycle's plan is a tensor of its own
             out = ops.mppi_closed_loop(prm, self.controller, self.simulator, st, *fl, goal, U, 1, 0 if smoothed else substeps, sim_dt, n_samples, iters,
                                        sigma, temperature, seed=seed, cycle_base=c, shift=sh, spheres=spheres, obstacle_weight=obstacle_weight, wind=wind,
-                                       want_plan=log or smoothed, clearance=clr, want_clearance=not smoothed)
+                                       want_plan=log or smoothed, clearance=clr, want_clearance=not smoothed, sphere_vel=sphere_velocities,
+                                       sphere_t0=sphere_t0 + (c * substeps) * sim_dt if smoothed else sphere_t0)
             clr = out["clearance"]
             traces.append(out["trace"])
             if smoothed:
@@ -294,7 +305,8 @@ class ClosedLoopMonteCarlo:
 
     def run_mppi_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float,
                        temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None,
-                       nominal=None, log: bool = False, smoother=None, mixer=None, motor_health=None):
+                       nominal=None, log: bool = False, smoother=None, mixer=None, motor_health=None, sphere_velocities=None,
+                       sphere_t0: float = 0.0):
         """:meth:`run_mppi` in ONE launch: every drone's `cycles` planning cycles inside one kernel, the plan never leaving the chip.  Same
         code, same bits as :meth:`run_mppi`, same arguments and the same shift rule (shift=None: ``floor(substeps * sim_dt / params.dt +
         0.5)`` clipped to [0, N]).  `log` keeps the last cycle's plan only: logs = [dict(plan_last, trace, cost)] with one entry.
@@ -303,7 +315,8 @@ class ClosedLoopMonteCarlo:
         form, 9 - 16 % ahead of the per-cycle chain of se3mpc_mppi_* + se3mpc_rollout_cost_grad_* + se3mpc_extract_* + se3mpc_closed_loop_*.
         At 4096 drones it is 17 - 27 % SLOWER than that chain (the kernel holds the controller's registers, so the MPPI phase runs at three
         (float32) / two (float64) wavefronts per SIMD instead of four, and one lane per workgroup flies while the others wait): for thousands of
-        drones drive the chain (``tools/gpu_probe_mppi_closed_loop.py``, ``chain_form``) unless the clearance output is what you need."""
+        drones drive the chain (``tools/gpu_probe_mppi_closed_loop.py``, ``chain_form``) unless the clearance output is what you need.
+        sphere_velocities, sphere_t0: as in :meth:`run_mppi` -- the table advances through all `cycles` inside the one kernel."""
         self._no_smoother(smoother, "run_mppi_fused")
         self._no_mixer(mixer, motor_health, "run_mppi_fused")
         st, sm, fl = self._start(p0, v0)
@@ -311,14 +324,14 @@ class ClosedLoopMonteCarlo:
         sh = self.resolve_shift(substeps, sim_dt, shift)
         out = self.ops.mppi_closed_loop(self.params, self.controller, self.simulator, st, *fl, goal, U, cycles, substeps, sim_dt,
                                         n_samples, iters, sigma, temperature, seed=seed, cycle_base=0, shift=sh, spheres=spheres,
-                                        obstacle_weight=obstacle_weight, wind=wind, want_plan=log)
+                                        obstacle_weight=obstacle_weight, wind=wind, want_plan=log, sphere_vel=sphere_velocities, sphere_t0=sphere_t0)
         logs = [dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"])] if log else []
         return self._result(st, sm, fl, logs=logs, U=U, cost=out["cost"], trace=out["trace"], clearance=out["clearance"])
 
     def run_mppi_fused_staged(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float,
                               temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None,
                               shift: Optional[int] = None, nominal=None, log: bool = False, smoother: Optional[SmootherParams] = None,
-                              mixer: Optional[MixerParams] = None, motor_health=None):
+                              mixer: Optional[MixerParams] = None, motor_health=None, sphere_velocities=None, sphere_t0: float = 0.0):
         """:meth:`run_mppi` with `smoother` and / or `mixer` (and `motor_health`) in ONE launch (``se3mpc_mppi_closed_loop_staged_*``): every
         cycle's MPPI iterations, update_trajectory and control / mixer / simulator steps inside one kernel, where :meth:`run_mppi` makes
         three launches per cycle -- and with ``clearance`` (B,) filled in whenever there are spheres, which the chain cannot measure.  Same
@@ -333,6 +346,7 @@ class ClosedLoopMonteCarlo:
         forms measured suggests this one for small batches, where the chain is launch-bound, and :meth:`run_mppi` for
         thousands of drones -- one lane per workgroup flies the act phase, and with both stages the MPPI phase runs at two (float32) / one
         (float64) wavefront per SIMD -- unless the clearance, which only this form measures with the stages, or one enqueue is what you need."""
+        self._no_moving(sphere_velocities, "run_mppi_fused_staged")
         self._mixer_option(mixer, motor_health)
         ops = self.ops
         st, sm, fl = self._start(p0, v0, smoother)
@@ -349,7 +363,8 @@ class ClosedLoopMonteCarlo:
 
     def run_mppi_edge(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
                       seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None, nominal=None,
-                      latency_depth: int = 5, onboard: Optional[OnboardParams] = None, log: bool = False):
+                      latency_depth: int = 5, onboard: Optional[OnboardParams] = None, log: bool = False, sphere_velocities=None,
+                      sphere_t0: float = 0.0):
         """The receding-horizon Monte-Carlo with MPPI as the planner on the reference's edge loop (edge/main.py:80-95), as a chain of two
         launches per cycle: ``se3mpc_mppi_closed_loop_*`` as the planner alone (one cycle, no simulator steps, on a scratch geometric-controller
         record it leaves untouched; arguments and shift rule as :meth:`run_mppi`), then ONE ``se3mpc_edge_loop_*`` launch of `substeps` x
@@ -362,6 +377,7 @@ class ClosedLoopMonteCarlo:
         this chain's time for 256 drones and 0.98 - 1.05 for 4096 at 256 samples x 8 iterations, N = 30: DESIGN.md 5.8e; other shapes: not measured);
         this chain stays the form with per-step logs."""
         import torch
+        self._no_moving(sphere_velocities, "run_mppi_edge")
         ops, prm = self.ops, self.params
         B, N = p0.shape[0], prm.horizon
         op = onboard if onboard is not None else ops.lib.onboard_default_params()
@@ -390,7 +406,8 @@ class ClosedLoopMonteCarlo:
 
     def run_mppi_edge_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float,
                             temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None,
-                            nominal=None, latency_depth: int = 5, onboard: Optional[OnboardParams] = None, want_last_plan: bool = False):
+                            nominal=None, latency_depth: int = 5, onboard: Optional[OnboardParams] = None, want_last_plan: bool = False,
+                            sphere_velocities=None, sphere_t0: float = 0.0):
         """:meth:`run_mppi_edge` in ONE launch (``se3mpc_mppi_closed_loop_edge_*``): every cycle's MPPI iterations and its
         `substeps` x (latency push -> OnboardController -> DroneSimulator.step) inside one kernel, the plan never leaving the chip, where
         :meth:`run_mppi_edge` makes two launches per cycle -- and with ``clearance`` (B,) filled in whenever there are spheres, which the chain
@@ -407,6 +424,7 @@ class ClosedLoopMonteCarlo:
         the clearance or one enqueue is what you need; for thousands of drones without spheres :meth:`run_mppi_edge` is a few per cent faster.  Other
         batch sizes, sample counts and horizons: not measured; :meth:`run_mppi_edge` stays the form with per-step logs."""
         import torch
+        self._no_moving(sphere_velocities, "run_mppi_edge_fused")
         ops = self.ops
         B = p0.shape[0]
         op = onboard if onboard is not None else ops.lib.onboard_default_params()

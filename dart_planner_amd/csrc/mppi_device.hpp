@@ -56,8 +56,18 @@ __device__ __forceinline__ R box_clip(const DevParams<R>& q, int a, R t) {
   return fmin(fmax(t, lo), hi);
 }
 
+// What a context of MOVING spheres adds (se3mpc_mppi_moving_*): the velocity table and the time of every step of the
+// horizon in the kernel's type, both in LDS.  The static context holds neither: Ctx<R> is the struct it always was.
+template <typename R, bool MOVING>
+struct CtxMotion {};
 template <typename R>
-struct Ctx {
+struct CtxMotion<R, true> {
+  const R* svel;    // LDS [K][3] = (vx, vy, vz)
+  const R* stime;   // LDS [N]: tR_k = (R)tau_k, the time of the state before step k on the table's clock
+};
+
+template <typename R, bool MOVING = false>
+struct Ctx : CtxMotion<R, MOVING> {
   DevParams<R> q;
   uint32_t key0, key1, qi, g;
   const R* U;       // LDS [3N]
@@ -69,8 +79,8 @@ struct Ctx {
 
 // Sample s at step k: the noise (raw words / normals optional) and the clipped thrust.  The one expression mppi_samples_kernel and
 // the fused kernel share, so the two agree bit for bit.
-template <typename R>
-__device__ __forceinline__ void draw(const Ctx<R>& c, const R* Uk, uint32_t s, int k, R sig, R t[3], uint32_t* raw = nullptr, R* nrm = nullptr) {
+template <typename R, bool MOVING>
+__device__ __forceinline__ void draw(const Ctx<R, MOVING>& c, const R* Uk, uint32_t s, int k, R sig, R t[3], uint32_t* raw = nullptr, R* nrm = nullptr) {
   uint32_t x[4] = {c.qi, s, c.g, (uint32_t)k};
   philox4x32_10(x, c.key0, c.key1);
   R n[3];
@@ -87,9 +97,10 @@ struct Roll {
   R sp, sterm, sv, sa, st, pen;
 };
 
-// One step of the forward sweep (planner.py:449-460 solved forward, the objective of :516-550, the sphere penalty on P_k)
-template <typename R>
-__device__ __forceinline__ void roll_step(const Ctx<R>& c, Roll<R>& r, int k, const R t[3]) {
+// One step of the forward sweep (planner.py:449-460 solved forward, the objective of :516-550, the sphere penalty on P_k).  MOVING: sphere
+// j's centre at step k is c_j + v_j * tR_k (one multiply-add per axis; v_j = 0 leaves c_j exactly), then the same expression.
+template <typename R, bool MOVING>
+__device__ __forceinline__ void roll_step(const Ctx<R, MOVING>& c, Roll<R>& r, int k, const R t[3]) {
   const DevParams<R>& q = c.q;
   R acc[3];
 #pragma unroll
@@ -102,9 +113,16 @@ __device__ __forceinline__ void roll_step(const Ctx<R>& c, Roll<R>& r, int k, co
     r.sa += acc[a] * acc[a];
     r.st += dev * dev;
   }
+  [[maybe_unused]] R tR = (R)0;
+  if constexpr (MOVING) tR = c.stime[k];
   for (int j = 0; j < c.K; ++j) {
     const R* s4 = c.sph + 4 * j;
-    const R dx = r.p[0] - s4[0], dy = r.p[1] - s4[1], dz = r.p[2] - s4[2];
+    R cx = s4[0], cy = s4[1], cz = s4[2];
+    if constexpr (MOVING) {
+      const R* v3 = c.svel + 3 * j;
+      cx = cx + v3[0] * tR; cy = cy + v3[1] * tR; cz = cz + v3[2] * tR;
+    }
+    const R dx = r.p[0] - cx, dy = r.p[1] - cy, dz = r.p[2] - cz;
     const R cc = dz * dz + (dy * dy + (dx * dx - s4[3]));
     const R h = fmax((R)0, -cc);
     r.pen += h * h;
@@ -128,8 +146,8 @@ __device__ __forceinline__ void roll_state_step(const DevParams<R>& q, R p[3], R
   }
 }
 
-template <typename R>
-__device__ __forceinline__ Roll<R> roll_begin(const Ctx<R>& c) {
+template <typename R, bool MOVING>
+__device__ __forceinline__ Roll<R> roll_begin(const Ctx<R, MOVING>& c) {
   Roll<R> r;
 #pragma unroll
   for (int a = 0; a < 3; ++a) { r.p[a] = c.p0[a]; r.v[a] = c.v0[a]; }
@@ -137,8 +155,8 @@ __device__ __forceinline__ Roll<R> roll_begin(const Ctx<R>& c) {
   return r;
 }
 
-template <typename R>
-__device__ __forceinline__ R roll_total(const Ctx<R>& c, const Roll<R>& r) {
+template <typename R, bool MOVING>
+__device__ __forceinline__ R roll_total(const Ctx<R, MOVING>& c, const Roll<R>& r) {
   const DevParams<R>& q = c.q;
   R cost = q.wv * r.sv + q.wa * r.sa + q.wT * r.st;
   if (q.has_goal) cost += q.wp * (r.sp + r.sterm) + q.term * q.wp * r.sterm;
@@ -146,8 +164,8 @@ __device__ __forceinline__ R roll_total(const Ctx<R>& c, const Roll<R>& r) {
 }
 
 // Cost of sample s (NOISE) or of the nominal as it stands (!NOISE: no draw, no clip -- the final evaluation)
-template <typename R, bool NOISE>
-__device__ __forceinline__ R sample_cost(const Ctx<R>& c, uint32_t s, R sig) {
+template <typename R, bool NOISE, bool MOVING>
+__device__ __forceinline__ R sample_cost(const Ctx<R, MOVING>& c, uint32_t s, R sig) {
   Roll<R> r = roll_begin(c);
   for (int k = 0; k < c.q.N; ++k) {
     R t[3];
@@ -173,6 +191,18 @@ __host__ __device__ inline Lds lds_layout(int N, int K, int W, size_t esz) {
   l.sph = align16(l.U + (size_t)3 * N * esz);
   l.total = align16(l.sph + (size_t)4 * K * esz);
   return l;
+}
+
+// Behind that image, the kernels of moving spheres keep: vel [K][3] R | step times [N] R
+struct MovingLds {
+  size_t vel, time, total;
+};
+__host__ __device__ inline MovingLds moving_lds_layout(int N, int K, int W, size_t esz) {
+  MovingLds m;
+  m.vel = lds_layout(N, K, W, esz).total;
+  m.time = align16(m.vel + (size_t)3 * K * esz);
+  m.total = align16(m.time + (size_t)N * esz);
+  return m;
 }
 
 // The image as pointers
@@ -201,10 +231,11 @@ __device__ __forceinline__ void stage_spheres(const DevParams<R>& q, const R* __
   }
 }
 
-template <typename R>
-__device__ __forceinline__ Ctx<R> load_ctx(const DevParams<R>& q, int ld, int p, uint32_t key0, uint32_t key1, uint32_t qi, const R* p0,
-                                           const R* v0, const R* goal, const R* U, const R* sph, int K, R w_obs) {
-  Ctx<R> c;
+// (MOVING: the caller sets svel and stime)
+template <typename R, bool MOVING = false>
+__device__ __forceinline__ Ctx<R, MOVING> load_ctx(const DevParams<R>& q, int ld, int p, uint32_t key0, uint32_t key1, uint32_t qi, const R* p0,
+                                                   const R* v0, const R* goal, const R* U, const R* sph, int K, R w_obs) {
+  Ctx<R, MOVING> c;
   c.q = q; c.key0 = key0; c.key1 = key1; c.qi = qi; c.g = 0; c.U = U; c.sph = sph; c.K = K; c.w_obs = w_obs;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -220,8 +251,8 @@ __device__ __forceinline__ Ctx<R> load_ctx(const DevParams<R>& q, int ld, int p,
 // wavefront partials folded in wavefront order, chunks folded in chunk order with the streaming rescale.  Returns the minimum cost m of
 // the range (+inf when every cost is NaN) and leaves acc[r] = sum_s w_s T_s[r] (r < 3N), acc[3N] = sum_s w_s, w_s = exp(-(c_s - m) / lambda),
 // in LDS, visible to the whole workgroup.
-template <typename R>
-__device__ __forceinline__ double weighted_pass(const Ctx<R>& c, const R* U, int s_lo, int count, R sigma, double inv_lam, double* acc, double* part,
+template <typename R, bool MOVING>
+__device__ __forceinline__ double weighted_pass(const Ctx<R, MOVING>& c, const R* U, int s_lo, int count, R sigma, double inv_lam, double* acc, double* part,
                                                 double* red) {
   const int N = c.q.N, rows = 3 * N, NT = (int)blockDim.x, W = NT / kWave;
   const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
@@ -296,8 +327,8 @@ __device__ __forceinline__ void shift_nominal(const DevParams<R>& q, R* U, R* tm
 }
 
 // Cost and argmin key of the nominal as it stands, written by lane 0 of the calling wavefront (the tail of every MPPI entry point)
-template <typename R>
-__device__ __forceinline__ void write_nominal_cost(const Ctx<R>& c, int p, uint32_t index_base, R* cost_out, uint64_t* keys) {
+template <typename R, bool MOVING>
+__device__ __forceinline__ void write_nominal_cost(const Ctx<R, MOVING>& c, int p, uint32_t index_base, R* cost_out, uint64_t* keys) {
   const R cf = sample_cost<R, false>(c, 0u, (R)0);
   if ((threadIdx.x & (kWave - 1)) == 0) {
     cost_out[p] = cf;
@@ -337,6 +368,13 @@ static int check_mppi_args(const char* fn, const se3mpc_params* p, int nprob, in
   if (K < 0 || K > SE3MPC_MAX_SPHERES) return fail(SE3MPC_ERR_SHAPE, "K outside [0, SE3MPC_MAX_SPHERES]", fn);
   if (!(temperature > 0.0) || !std::isfinite(temperature)) return fail(SE3MPC_ERR_PARAM, "temperature must be finite and > 0", fn);
   if (!(obstacle_weight >= 0.0) || !std::isfinite(obstacle_weight)) return fail(SE3MPC_ERR_PARAM, "obstacle_weight must be finite and >= 0", fn);
+  return SE3MPC_OK;
+}
+
+// ... and what the entries of moving spheres add (se3mpc_mppi_moving_*, se3mpc_mppi_closed_loop_moving_*), after the rules above
+static int check_moving_args(const char* fn, int K, const void* sphere_vel, double sphere_t0) {
+  if (!std::isfinite(sphere_t0)) return fail(SE3MPC_ERR_PARAM, "sphere_t0 must be finite", fn);
+  if (K > 0 && sphere_vel == nullptr) return fail(SE3MPC_ERR_NULL, "sphere_vel is NULL with K > 0", fn);
   return SE3MPC_OK;
 }
 

@@ -13,20 +13,21 @@ constexpr int kPark = 64;     // simulator positions parked per clearance reduct
 
 // LDS behind the planner's image (bytes, 16-byte aligned regions): stamps [N] double | time [1] double | controller record
 // [SE3MPC_CONTROLLER_STATE_WORDS] double | plan P, V, A [3][N][3] R | pos, vel, att, omega, wind, goal, clearance [19] R | raw radii [K] R | parked positions
-// [kPark][3] R
+// [kPark][3] R.  moving (the kernel of moving spheres): the image lies behind moving_lds_layout's and a parked row is
+// (x, y, z, tR) -- the position a simulator step produced and the time it is measured at, in the kernel's type.
 struct LoopLds {
   size_t stamps, time, ctrl, plan, vec, rad, park, total;
 };
-__host__ __device__ inline LoopLds loop_lds_layout(int N, int K, int W, size_t esz) {
+__host__ __device__ inline LoopLds loop_lds_layout(int N, int K, int W, size_t esz, bool moving = false) {
   LoopLds x;
-  x.stamps = lds_layout(N, K, W, esz).total;
+  x.stamps = moving ? moving_lds_layout(N, K, W, esz).total : lds_layout(N, K, W, esz).total;
   x.time = x.stamps + (size_t)N * 8;
   x.ctrl = x.time + 8;
   x.plan = align16(x.ctrl + (size_t)SE3MPC_CONTROLLER_STATE_WORDS * 8);
   x.vec = align16(x.plan + (size_t)9 * N * esz);
   x.rad = align16(x.vec + 19 * esz);
   x.park = align16(x.rad + (size_t)K * esz);
-  x.total = align16(x.park + (size_t)3 * kPark * esz);
+  x.total = align16(x.park + (size_t)(moving ? 4 : 3) * kPark * esz);
   return x;
 }
 
@@ -47,15 +48,24 @@ __device__ __forceinline__ void hand_over_plan(const DevParams<R>& q, R p[3], R 
 
 // The clearance of the n positions an act chunk parked, by the whole workgroup: min over (step, j) of |pos - c_j| - r_j (sph rows (cx, cy,
 // cz, .), raw radii rad) folded into *running by the first lane -- wavefront min, then the W partials in wavefront order through red [W].
-// The positions are visible to every lane on entry; ends with the workgroup synchronised.
-template <typename R>
-__device__ __forceinline__ void clearance_chunk(const R* park, const R* sph, const R* rad, int n, int K, double* red, R* running) {
+// The positions are visible to every lane on entry; ends with the workgroup synchronised.  MOVING: park rows are (x, y, z, tR) and sphere j's
+// centre is c_j + svel_j * tR (svel [K][3]); the distance keeps its form.
+template <typename R, bool MOVING = false>
+__device__ __forceinline__ void clearance_chunk(const R* park, const R* sph, const R* rad, int n, int K, double* red, R* running,
+                                                const R* svel = nullptr) {
   const int NT = (int)blockDim.x, W = NT / kWave;
   const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   R ml = (R)__builtin_huge_val();
   for (int i = tid; i < n * K; i += NT) {
     const int step = i / K, j = i - step * K;
-    const R dx = park[3 * step] - sph[4 * j], dy = park[3 * step + 1] - sph[4 * j + 1], dz = park[3 * step + 2] - sph[4 * j + 2];
+    R dx, dy, dz;
+    if constexpr (MOVING) {
+      const R tR = park[4 * step + 3];
+      const R cx = sph[4 * j] + svel[3 * j] * tR, cy = sph[4 * j + 1] + svel[3 * j + 1] * tR, cz = sph[4 * j + 2] + svel[3 * j + 2] * tR;
+      dx = park[4 * step] - cx; dy = park[4 * step + 1] - cy; dz = park[4 * step + 2] - cz;
+    } else {
+      dx = park[3 * step] - sph[4 * j]; dy = park[3 * step + 1] - sph[4 * j + 1]; dz = park[3 * step + 2] - sph[4 * j + 2];
+    }
     ml = fmin(ml, sqrt(dx * dx + dy * dy + dz * dz) - rad[j]);
   }
   const double wm = wave_min((double)ml);

@@ -107,6 +107,14 @@ class Ops:
             raise ValueError(f"spheres: expected (K<={SE3MPC_MAX_SPHERES}, 4) {suf}, got {tuple(spheres.shape)}")
         return spheres.shape[0]
 
+    def _sphere_vel(self, sphere_vel, sphere_t0, K: int, suf) -> tuple:
+        """The velocity table (K, 3) rows (vx, vy, vz) beside a sphere table of K rows -> the two arguments the moving entries take
+        after ``spheres``."""
+        self.be.check(sphere_vel, "sphere_vel")
+        if sphere_vel.ndim != 2 or tuple(sphere_vel.shape) != (K, 3) or self.be.suffix(sphere_vel) != suf:
+            raise ValueError(f"sphere_vel: expected ({K}, 3) {suf} beside the sphere table, got {tuple(sphere_vel.shape)}")
+        return (self.be.ptr(sphere_vel if K else None), float(sphere_t0))
+
     @staticmethod
     def _B(ld: int, B: Optional[int]) -> int:
         B = ld if B is None else int(B)
@@ -435,14 +443,15 @@ class Ops:
         return self._same(U, p0, v0, goal if params.has_goal else None), U.shape[1]
 
     def _mppi_call(self, base, tail, params, p0, v0, goal, U, n_samples, iters, sigma, temperature, seed, iter_base, index_base, spheres,
-                   obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out):
+                   obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out, sphere_vel=None, sphere_t0=0.0):
         """The operand checks, output allocation and call shared by :meth:`mppi` and :meth:`mppi_split`; ``tail``: the arguments between
-        ``keys`` and ``stream``."""
+        ``keys`` and ``stream``; ``sphere_vel``: the moving entry's two arguments go in after ``spheres``."""
         suf, ld = self._mppi_operands(params, U, p0, v0, goal)
         N = params.horizon
         K = 0
         if spheres is not None:
             K = self._spheres(spheres, suf)
+        motion = () if sphere_vel is None else self._sphere_vel(sphere_vel, sphere_t0, K, suf)
         if out is not None:
             U_out, cost, trace, keys = out
         else:
@@ -452,20 +461,26 @@ class Ops:
             keys = self.be.empty((ld,), "i64") if want_keys else None
         self.lib.call(base, suf, self._B(ld, B), ld, int(n_samples), int(iters), float(sigma), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
                       int(iter_base) & 0xFFFFFFFF, self.be.ptr(iter_offset), int(index_base) & 0xFFFFFFFF, self.be.ptr(p0), self.be.ptr(v0),
-                      self.be.ptr(goal if params.has_goal else None), self.be.ptr(U), self.be.ptr(U_out), self.be.ptr(spheres if K else None), K,
+                      self.be.ptr(goal if params.has_goal else None), self.be.ptr(U), self.be.ptr(U_out), self.be.ptr(spheres if K else None), *motion, K,
                       float(obstacle_weight), self.be.ptr(cost), self.be.ptr(trace), self.be.ptr(keys), *tail, self.be.stream(),
                       params=params)
         return dict(U=U_out, cost=cost, trace=trace if (trace is None or iters > 0) else trace[:0], keys=keys)
 
     def mppi(self, params: Params, p0, v0, goal, U, n_samples: int, iters: int, sigma: float, temperature: float, seed: int = 0,
              iter_base: int = 0, index_base: int = 0, spheres=None, obstacle_weight: float = 0.0, U_out=None, want_trace: bool = True,
-             want_keys: bool = True, iter_offset=None, B: Optional[int] = None, out=None):
+             want_keys: bool = True, iter_offset=None, B: Optional[int] = None, out=None, sphere_vel=None, sphere_t0: float = 0.0):
         """`iters` MPPI iterations of every problem in ONE launch (``se3mpc_mppi_*``, one workgroup per problem): perturb the nominal U
         (3N, ld) with Philox normals of std `sigma`, roll the `n_samples` samples out, weight by exp(-(cost - min) / temperature) and move U
         to the weighted mean.  p0, v0, goal: (3, ld); spheres: (K, 4) rows (cx, cy, cz, r), same dtype, shared by all problems.
         -> dict(U (3N, ld), cost (ld,) with the penalty at U, trace (iters, ld) | None = the minimum sample cost per iteration,
         keys int64 (ld,) | None = the argmin key of each problem's cost).  U_out may be U (in place); iter_offset: int32 (1,) device
-        word added to iter_base (graph replays); ``out`` = (U_out, cost, trace, keys) reuses preallocated outputs."""
+        word added to iter_base (graph replays); ``out`` = (U_out, cost, trace, keys) reuses preallocated outputs.
+        sphere_vel: None, or (K, 3) rows (vx, vy, vz), same dtype: the spheres move with constant velocity and step k is penalised against
+        the centres at sphere_t0 + k dt seconds after the time the table holds (``se3mpc_mppi_moving_*``; keep sphere_t0 small, the kernel
+        rounds the time to its own type)."""
+        if sphere_vel is not None:
+            return self._mppi_call("mppi_moving", (), params, p0, v0, goal, U, n_samples, iters, sigma, temperature, seed, iter_base,
+                                   index_base, spheres, obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out, sphere_vel, sphere_t0)
         return self._mppi_call("mppi", (), params, p0, v0, goal, U, n_samples, iters, sigma, temperature, seed, iter_base,
                                index_base, spheres, obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out)
 
@@ -734,14 +749,17 @@ class Ops:
                          cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
                          seed: int = 0, cycle_base: int = 0, shift: int = 1, iter_base: int = 0, index_base: int = 0, spheres=None,
                          obstacle_weight: float = 0.0, wind=None, want_trace: bool = True, want_plan: bool = False, clearance=None,
-                         want_clearance: bool = True):
+                         want_clearance: bool = True, sphere_vel=None, sphere_t0: float = 0.0):
         """se3mpc_mppi_closed_loop_*: `cycles` x (`iters` MPPI iterations from the drone's own state on its nominal, the plan handed to the
         controller on the chip, `substeps` control + simulator steps, the nominal shifted by `shift` rows) for B drones in ONE launch, in
         place on (state, time, pos, vel, att, omega) and on the nominals U (B, N, 3).  goal (B, 3); spheres (K, 4) rows (cx, cy, cz, r)
         shared by all drones; wind None, (3,) or (B, 3) newtons.  clearance: a (B,) running minimum to continue (updated in place), or None:
         a fresh one at +inf when `want_clearance` and there are spheres.
         -> dict(U (B, N, 3) = the next cycle's starting nominal, cost (B,) at the last cycle's nominal, trace (B, cycles, iters) | None,
-        plan_last (B, 3, N, 3) = P, V, A of the last cycle's plan | None, clearance (B,) | None)."""
+        plan_last (B, 3, N, 3) = P, V, A of the last cycle's plan | None, clearance (B,) | None).
+        sphere_vel: None, or (K, 3) rows (vx, vy, vz): the spheres move with constant velocity (``se3mpc_mppi_closed_loop_moving_*``);
+        sphere_t0: the time of the RUN's start (cycle 0) after the time the table holds, the same in every chained call -- plan and
+        clearance take the centres at the time of the step they look at."""
         B = pos.shape[0]
         suf = self.be.suffix(pos)
         N = params.horizon
@@ -762,9 +780,10 @@ class Ops:
         cost = self.be.empty((B,), suf)
         trace = self.be.empty((B, max(int(cycles), 1), max(int(iters), 1)), suf) if want_trace else None
         plan = self.be.empty((B, 3, N, 3), suf) if want_plan else None
-        self.lib.loop_call("mppi_closed_loop", suf, params, cp, sp, B, int(cycles), int(substeps), float(sim_dt), int(cycle_base) & 0xFFFFFFFF,
+        motion = () if sphere_vel is None else self._sphere_vel(sphere_vel, sphere_t0, K, suf)
+        self.lib.loop_call("mppi_closed_loop" if sphere_vel is None else "mppi_closed_loop_moving", suf, params, cp, sp, B, int(cycles), int(substeps), float(sim_dt), int(cycle_base) & 0xFFFFFFFF,
                            int(shift), int(n_samples), int(iters), float(sigma), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                           int(iter_base) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF, self.be.ptr(goal), self.be.ptr(spheres if K else None), K,
+                           int(iter_base) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF, self.be.ptr(goal), self.be.ptr(spheres if K else None), *motion, K,
                            float(obstacle_weight), self.be.ptr(wind), w_stride, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel),
                            self.be.ptr(att), self.be.ptr(omega), self.be.ptr(state), self.be.ptr(U), self.be.ptr(cost), self.be.ptr(trace),
                            self.be.ptr(plan), self.be.ptr(clearance), self.be.stream())

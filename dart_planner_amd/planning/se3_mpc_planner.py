@@ -83,6 +83,7 @@ class SE3MPCPlanner(BasePlanner):
         self.hover_thrust = self.mass * self.gravity
         self.goal_position: Optional[np.ndarray] = None
         self.obstacles: List[Tuple[np.ndarray, float]] = []
+        self.moving_obstacles: List[Tuple[np.ndarray, float, np.ndarray, float]] = []      # (centre, radius, velocity, timestamp)
         # planner.py:158-159.  The reference never assigns last_solution, so its warm start
         # (_create_warm_start, :294-327) is dead code and every solve is a cold start.  With
         # receding_horizon=True this planner does what that code intended: it keeps the last solution
@@ -141,8 +142,19 @@ class SE3MPCPlanner(BasePlanner):
         r = float(ensure_units(radius, "m", "SE3MPCPlanner.add_obstacle radius"))
         self.obstacles.append((c, r))
 
+    def add_moving_obstacle(self, center, radius, velocity, timestamp: float) -> None:
+        """A sphere that moves with constant `velocity` (m/s): its centre is `center` at `timestamp`, on the clock of
+        ``DroneState.timestamp``.  :meth:`plan_mppi` and :meth:`plan_batch_mppi` penalise every step of the horizon against the centre at
+        that step's time (``se3mpc_mppi_moving_*``, DESIGN.md 5.8f) and :meth:`obstacle_clearance` evaluates it at each row's timestamp;
+        :meth:`plan_shooting` and the constraint helpers of the L-BFGS-B path see a snapshot at the state's timestamp."""
+        c = np.array(ensure_units(center, "m", "SE3MPCPlanner.add_moving_obstacle center"), dtype=float)
+        r = float(ensure_units(radius, "m", "SE3MPCPlanner.add_moving_obstacle radius"))
+        v = np.array(to_float(velocity), dtype=float).reshape(3)
+        self.moving_obstacles.append((c, r, v, float(timestamp)))
+
     def clear_obstacles(self) -> None:
         self.obstacles.clear()
+        self.moving_obstacles.clear()
 
     def sense(self, current_state: DroneState, goal_position):
         goal_position = ensure_units(goal_position, "m", "SE3MPCPlanner.sense goal_position")
@@ -381,6 +393,24 @@ class SE3MPCPlanner(BasePlanner):
         sph = np.asarray(obstacles, float).reshape(-1, 4)
         return sph if len(sph) else None
 
+    def _moving_obstacle_table(self, obstacles, now: float) -> Optional[np.ndarray]:
+        """(K, 7) rows (cx, cy, cz, r, vx, vy, vz) holding at time `now` (the state's timestamp), for the entries of moving spheres, which
+        then take sphere_t0 = 0: `obstacles` as in :meth:`_obstacle_table`, the planner's own list being its static obstacles (zero velocity)
+        followed by its moving ones, each centre rebased in float64 on the host, c + v * (now - timestamp) -- the kernels round times to
+        their own type, and a float32 epoch time has an ulp of minutes.  An array may be (K, 4) (static) or (K, 7) (taken to hold at
+        `now`).  None when there is nothing to avoid."""
+        if obstacles is False:
+            return None
+        if obstacles is None or obstacles is True:
+            rows = [[*np.asarray(to_float(c), float).reshape(3), float(r), 0.0, 0.0, 0.0] for c, r in self.obstacles]
+            rows += [[*(c + v * (float(now) - t)), r, *v] for c, r, v, t in self.moving_obstacles]
+            return np.array(rows, dtype=float) if rows else None
+        a = np.asarray(obstacles, float)
+        if a.ndim == 2 and a.shape[1] == 7:
+            return a.copy() if len(a) else None
+        sph = a.reshape(-1, 4)
+        return np.concatenate([sph, np.zeros((len(sph), 3))], axis=1) if len(sph) else None
+
     def plan_shooting(self, current_state: DroneState, goal_position, n_samples: int = 8192, iters: int = 16, step: float = 0.9,
                       sigma: float = 2.0, seed: int = 0, precision: str = "f32", obstacles=None,
                       obstacle_weight: Optional[float] = None) -> Trajectory:
@@ -393,7 +423,8 @@ class SE3MPCPlanner(BasePlanner):
         obstacles: the sphere list the descent avoids (``_obstacle_table``: by default the planner's own, which the reference keeps and
         never uses) through the obstacle-aware loop ``se3mpc_rollout_iterate_obstacles_*``: the objective gains
         obstacle_weight * sum max(0, -(|P_k - c_j|^2 - (r_j + safety_margin)^2))^2 (obstacle_weight defaults to the config's, planner.py:63);
-        ``last_result["penalty"]`` is what is left of it at the returned plan (0 = every margin kept)."""
+        ``last_result["penalty"]`` is what is left of it at the returned plan (0 = every margin kept).  Moving obstacles
+        (:meth:`add_moving_obstacle`) are a snapshot at the state's timestamp: the descent does not move them along the horizon."""
         import torch
         import torch.distributed as dist
         from ..distributed import sharded_shooting_plan
@@ -403,7 +434,10 @@ class SE3MPCPlanner(BasePlanner):
         N = self.se3_config.prediction_horizon
         p0 = np.asarray(to_float(current_state.position), float)
         v0 = np.asarray(to_float(current_state.velocity), float)
-        sph = self._obstacle_table(obstacles)
+        if (self.moving_obstacles and (obstacles is None or obstacles is True)) or (np.ndim(obstacles) == 2 and np.shape(obstacles)[1] == 7):
+            sph = self._mppi_tables(obstacles, current_state.timestamp)[0]          # the snapshot at the state's timestamp
+        else:
+            sph = self._obstacle_table(obstacles)
         w_obs = float(self.se3_config.obstacle_weight if obstacle_weight is None else obstacle_weight)
         single = not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
         if single and getattr(ops.be, "graph_capable", False):
@@ -562,20 +596,31 @@ class SE3MPCPlanner(BasePlanner):
         ``splits``: None = one workgroup, one launch; an integer spreads the samples over that many workgroups (``se3mpc_mppi_split_*``,
         one launch per iteration and one more; n_samples must be a multiple of 64 * splits); "auto" = n_samples // 256, and the one-launch
         path where that is 1.
-        The split plan differs from the unsplit one in the last bits of its float64 sums only (``splits`` = 1: not at all)."""
+        The split plan differs from the unsplit one in the last bits of its float64 sums only (``splits`` = 1: not at all).
+        Moving obstacles (:meth:`add_moving_obstacle`, or an ``obstacles`` array of (K, 7) rows (cx, cy, cz, r, vx, vy, vz) holding at the
+        state's timestamp): with at least one non-zero velocity the plan is ``se3mpc_mppi_moving_*`` on the table rebased to the state's
+        timestamp (:meth:`_moving_obstacle_table`), launch by launch -- the EAGER path even on a graph-capable backend, since the rebased
+        table changes every call and the captured graph's pinned input does not carry it.  ``se3mpc_shooting_finish_*`` knows only static
+        spheres, so it runs without them: ``cost_with_penalty`` is the MPPI entry's own cost of the nominal (the moving penalty included),
+        ``cost`` the finish's running cost and ``penalty`` their difference.  The split form is not built: ``splits`` then raises
+        ValueError."""
         current_state, _, _ = self.sense(current_state, goal_position)
         ops = self._get_ops()
         prm = self._params()
         N = self.se3_config.prediction_horizon
         p0 = np.asarray(to_float(current_state.position), float)
         v0 = np.asarray(to_float(current_state.velocity), float)
-        sph = self._obstacle_table(obstacles)
+        sph, moving = self._mppi_tables(obstacles, current_state.timestamp)
         w_obs = float(self.se3_config.obstacle_weight if obstacle_weight is None else obstacle_weight)
         U0, shift = self._mppi_nominal(N, warm_start)
         it_base = getattr(self, "_mppi_iter_base", 0)
         splits = self._mppi_splits(splits, n_samples)
+        if moving is not None and splits is not None:
+            raise ValueError("plan_mppi: the split form is not built for moving obstacles (se3mpc_mppi_moving_* has no split entry): use splits=None")
         args = (ops, prm, p0, v0, U0, int(n_samples), int(iters), float(sigma), float(temperature), int(seed), precision, sph, w_obs, it_base, splits)
-        if getattr(ops.be, "graph_capable", False):
+        if moving is not None:
+            r, trace = self._plan_mppi_eager(*args, moving=moving)
+        elif getattr(ops.be, "graph_capable", False):
             r, trace = self._plan_mppi_captured(*args)
         else:
             r, trace = self._plan_mppi_eager(*args)
@@ -588,13 +633,35 @@ class SE3MPCPlanner(BasePlanner):
                "body_rates": blk(5), "thrusts": r[18 * N:19 * N].copy()}
         return self._create_trajectory_from_solution(sol, time.time())
 
-    def _plan_mppi_eager(self, ops, prm, p0, v0, U0, n_samples, iters, sigma, temperature, seed, precision, sph, w_obs, it_base, splits=None):
-        """plan_mppi launch by launch (any backend): -> (packed float64 result of se3mpc_shooting_finish_*, trace)."""
+    def _mppi_tables(self, obstacles, now: float):
+        """What the MPPI entries take: (the (K, 4) table for ``se3mpc_mppi_*`` | None, the (K, 7) table of :meth:`_moving_obstacle_table`
+        for ``se3mpc_mppi_moving_*`` when at least one sphere moves | None)."""
+        tab = self._moving_obstacle_table(obstacles, now)
+        if tab is None:
+            return None, None
+        return np.ascontiguousarray(tab[:, :4]), (tab if np.any(tab[:, 4:] != 0.0) else None)
+
+    def _plan_mppi_eager(self, ops, prm, p0, v0, U0, n_samples, iters, sigma, temperature, seed, precision, sph, w_obs, it_base, splits=None,
+                         moving=None):
+        """plan_mppi launch by launch (any backend): -> (packed float64 result of se3mpc_shooting_finish_*, trace).  moving: the (K, 7)
+        table of :meth:`_moving_obstacle_table` -- ``se3mpc_mppi_moving_*`` with sphere_t0 = 0, the finish without spheres and the packed
+        (cost, penalty, cost_with_penalty) completed from the MPPI entry's own cost."""
         N = prm.horizon
         be = ops.be
         suf = "f32" if precision == "f32" else "f64"
         col = lambda a, kind: be.from_host(np.ascontiguousarray(np.asarray(a, float).reshape(-1, 1).astype(np.float32 if kind == "f32" else np.float64)))
         state = be.from_host(np.concatenate([p0, v0, self.goal_position]).astype(np.float64))
+        if moving is not None:
+            npdt = np.float32 if suf == "f32" else np.float64
+            dev = lambda a: be.from_host(np.ascontiguousarray(a.astype(npdt)))
+            out = ops.mppi(prm, col(p0, suf), col(v0, suf), col(self.goal_position, suf), col(U0, suf), n_samples, iters, sigma, temperature, seed=seed,
+                           iter_base=it_base, spheres=dev(moving[:, :4]), obstacle_weight=w_obs, sphere_vel=dev(moving[:, 4:]), sphere_t0=0.0)
+            res = be.empty((19 * N + 3,), "f64")
+            ops.shooting_finish(prm, out["U"], out["keys"], state, res)
+            r = np.asarray(be.to_host(res), dtype=float).copy()
+            r[19 * N + 2] = float(np.asarray(be.to_host(out["cost"]), dtype=float)[0])
+            r[19 * N + 1] = r[19 * N + 2] - r[19 * N]
+            return r, np.asarray(be.to_host(out["trace"]), dtype=float)[:, 0].copy()
         sph_r = None if sph is None else be.from_host(np.ascontiguousarray(sph.astype(np.float32 if suf == "f32" else np.float64)))
         out = self._mppi_op(ops, splits, prm, col(p0, suf), col(v0, suf), col(self.goal_position, suf), col(U0, suf), n_samples, iters, sigma,
                             temperature, seed=seed, iter_base=it_base, spheres=sph_r, obstacle_weight=w_obs)
@@ -668,11 +735,13 @@ class SE3MPCPlanner(BasePlanner):
 
     def plan_batch_mppi(self, positions, velocities, goals, n_samples: int = MPPI_SAMPLES, iters: int = MPPI_ITERS, sigma: float = MPPI_SIGMA,
                         temperature: float = MPPI_TEMPERATURE, seed: int = 0, precision: Optional[str] = None, obstacles=None,
-                        obstacle_weight: Optional[float] = None, nominal=None, iter_base: int = 0, splits=None) -> Dict[str, np.ndarray]:
+                        obstacle_weight: Optional[float] = None, nominal=None, iter_base: int = 0, splits=None,
+                        timestamp: float = 0.0) -> Dict[str, np.ndarray]:
         """MPPI for B independent (state, goal) problems in ONE launch (problem b draws the noise of index b): positions, velocities, goals (B, 3);
         nominal (B, N, 3) or None = hover.  Returns arrays with a leading B axis: positions, velocities, thrust_vectors, accelerations,
         attitudes, body_rates (B, N, 3), thrusts (B, N), cost (B,) with the penalty, trace (B, iters).  ``splits`` as :meth:`plan_mppi`; "auto"
-        also keeps B * splits within 1024 workgroups."""
+        also keeps B * splits within 1024 workgroups.  Moving obstacles as :meth:`plan_mppi`: ``timestamp`` is the time all B states hold
+        (rebasing the planner's own moving obstacles); with a non-zero velocity the launch is ``se3mpc_mppi_moving_*`` and ``splits`` raises."""
         p0 = np.asarray(to_float(positions), float).reshape(-1, 3)
         v0 = np.asarray(to_float(velocities), float).reshape(-1, 3)
         g = np.asarray(to_float(goals), float).reshape(-1, 3)
@@ -685,12 +754,17 @@ class SE3MPCPlanner(BasePlanner):
         prm = self._params(has_goal=1)
         npdt = np.float32 if (precision or "f32") == "f32" else np.float64
         lane = lambda a: be.from_host(np.ascontiguousarray(np.asarray(a, float).reshape(B, -1).T.astype(npdt)))
-        sph = self._obstacle_table(obstacles)
+        sph, moving = self._mppi_tables(obstacles, timestamp)
         w_obs = float(self.se3_config.obstacle_weight if obstacle_weight is None else obstacle_weight)
         lp0, lv0, lg = lane(p0), lane(v0), lane(g)
+        more = {}
+        if moving is not None:
+            if self._mppi_splits(splits, n_samples, B) is not None:
+                raise ValueError("plan_batch_mppi: the split form is not built for moving obstacles: use splits=None")
+            more = dict(sphere_vel=be.from_host(np.ascontiguousarray(moving[:, 4:].astype(npdt))), sphere_t0=0.0)
         out = self._mppi_op(ops, self._mppi_splits(splits, n_samples, B), prm, lp0, lv0, lg, lane(U), n_samples, iters, sigma, temperature, seed=seed,
                             iter_base=iter_base, spheres=None if sph is None else be.from_host(np.ascontiguousarray(sph.astype(npdt))),
-                            obstacle_weight=w_obs, want_keys=False)
+                            obstacle_weight=w_obs, want_keys=False, **more)
         _, _, P, V = ops.rollout_cost_grad(prm, lp0, lv0, lg, out["U"], want_grad=False, want_states=True)
         acc, att, rates, thr = ops.extract(prm, out["U"])
         h = lambda a, shape: np.asarray(be.to_host(a), dtype=float).T.reshape(shape).copy()
@@ -758,8 +832,18 @@ class SE3MPCPlanner(BasePlanner):
     def obstacle_clearance(self, trajectory: Trajectory) -> Dict[str, float]:
         """planner.py:499-514 evaluated on a planned trajectory with the obstacle kernel: the minimum
         of |p_k - c_j|^2 - (r_j + margin)^2 over steps and obstacles (>= 0 means clear) and the summed
-        violation.  (The reference builds these constraints and never passes them to the solver.)"""
+        violation.  (The reference builds these constraints and never passes them to the solver.)  Moving obstacles
+        (:meth:`add_moving_obstacle`) are evaluated on the host at each row's own timestamp, c + v * (trajectory.timestamps[k] - timestamp),
+        with the same residual and the same violation sum_k sum_j max(0, -residual)."""
         import torch
+        if self.moving_obstacles:
+            P = np.asarray(to_float(trajectory.positions), float).reshape(-1, 3)
+            ts = np.asarray(trajectory.timestamps, float).reshape(-1)
+            margin = float(self.se3_config.safety_margin)
+            res = [np.sum((P - np.asarray(to_float(c), float).reshape(3)) ** 2, axis=1) - (float(r) + margin) ** 2 for c, r in self.obstacles]
+            res += [np.sum((P - (c[None] + v[None] * (ts - t)[:, None])) ** 2, axis=1) - (r + margin) ** 2 for c, r, v, t in self.moving_obstacles]
+            res = np.stack(res, axis=1)
+            return dict(min_residual=float(res.min()), violation=float(np.sum(np.maximum(0.0, -res))))
         if not self.obstacles:
             return dict(min_residual=float("inf"), violation=0.0)
         ops = self._get_ops()
@@ -806,6 +890,9 @@ class SE3MPCPlanner(BasePlanner):
         cons = [{"type": "eq", "fun": lambda x: self._dynamics_constraints(x, current_state, N)}]
         if self.obstacles:
             cons.append({"type": "ineq", "fun": lambda x: self._obstacle_constraints(x, N)})
+        if self.moving_obstacles:                                    # a snapshot at the state's timestamp (the reference has no moving obstacles)
+            snap = self._moving_obstacle_table(None, current_state.timestamp)[len(self.obstacles):, :4]
+            cons.append({"type": "ineq", "fun": lambda x: self._obstacle_constraints(x, N, snap)})
         return cons
 
     def _dynamics_constraints(self, x, current_state: DroneState, N: int) -> np.ndarray:             # :426-462
@@ -821,12 +908,13 @@ class SE3MPCPlanner(BasePlanner):
         ops = self._get_ops()
         return ops.be.to_host(ops.physical_constraints(self._params(horizon=N), self._lane1(x)))[:, 0].astype(float)
 
-    def _obstacle_constraints(self, x, N: int) -> np.ndarray:                                        # :499-514
+    def _obstacle_constraints(self, x, N: int, table=None) -> np.ndarray:                            # :499-514
         import torch
-        if not self.obstacles:
+        if table is None and not self.obstacles:
             return np.array([])
         ops = self._get_ops()
-        sph = torch.tensor([[*c, r] for c, r in self.obstacles], dtype=torch.float64, device=ops.be.device)
+        sph = torch.tensor([[*c, r] for c, r in self.obstacles] if table is None else np.asarray(table, float).tolist(), dtype=torch.float64,
+                           device=ops.be.device)
         C, _, _ = ops.obstacle_residual(self._params(horizon=N), self._lane1(x), sph, materialize=True)
         return ops.be.to_host(C)[:, 0].astype(float)
 

@@ -341,6 +341,25 @@ int se3mpc_mppi_f64(const se3mpc_params* p, int nprob, int ld, int S, int iters,
                     uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const double* p0, const double* v0, const double* goal,
                     const double* U_in, double* U_out, const double* spheres, int K, double obstacle_weight, double* cost, double* trace,
                     uint64_t* keys, void* stream);
+/* se3mpc_mppi_* around spheres that MOVE with constant velocity.  The operands of se3mpc_mppi_*, and after `spheres`:
+ * sphere_vel [K][3] rows (vx, vy, vz) in m/s, same type, shared by all problems; sphere_t0: the time of step 0 on the table's clock, i.e.
+ * the centres of `spheres` hold at time 0 of that clock and the plan starts sphere_t0 seconds later.  The penalty of step k (on the state
+ * before step k, as in se3mpc_mppi_*) is taken against the centres at
+ *   tau_k = sphere_t0 + (double)k * dt,     tR = tau_k rounded to the kernel's type,     centre_a = c_a + v_a * tR   (may be one FMA)
+ * and is then se3mpc_mppi_*'s expression dz^2 + (dy^2 + (dx^2 - (r + margin)^2)).  With sphere_vel = 0 the centre is exactly c for every
+ * finite tau and every output equals se3mpc_mppi_*'s bit for bit.  tR is tau in the KERNEL's type: keep sphere_t0 and the span of a run
+ * small (seconds since the table was made, not epoch time) -- a float32 kernel at tau = 1.7e9 has an ulp of 128 s.  Rebase the centres
+ * on the host in float64 instead (c + v * (now - t_table), sphere_t0 = 0).
+ * Checks: those of se3mpc_mppi_*, then a non-finite sphere_t0: SE3MPC_ERR_PARAM; sphere_vel NULL with K > 0: SE3MPC_ERR_NULL.  K = 0 is
+ * allowed and reads neither table.  There is no split form. */
+int se3mpc_mppi_moving_f32(const se3mpc_params* p, int nprob, int ld, int S, int iters, double sigma, double temperature, uint64_t seed,
+                           uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const float* p0, const float* v0,
+                           const float* goal, const float* U_in, float* U_out, const float* spheres, const float* sphere_vel, double sphere_t0,
+                           int K, double obstacle_weight, float* cost, float* trace, uint64_t* keys, void* stream);
+int se3mpc_mppi_moving_f64(const se3mpc_params* p, int nprob, int ld, int S, int iters, double sigma, double temperature, uint64_t seed,
+                           uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const double* p0, const double* v0,
+                           const double* goal, const double* U_in, double* U_out, const double* spheres, const double* sphere_vel,
+                           double sphere_t0, int K, double obstacle_weight, double* cost, double* trace, uint64_t* keys, void* stream);
 /* se3mpc_mppi_* with ONE problem's samples split over `splits` workgroups (split j owns samples [j S / splits, (j + 1) S / splits)), for
  * the call that plans one or a few problems and would otherwise run on one or a few compute units.  Same operands, same noise (the
  * counter (q, s, g, k) does not depend on who draws a sample), same cost, same update, same outputs as se3mpc_mppi_*; only the order of
@@ -937,6 +956,31 @@ int se3mpc_mppi_closed_loop_f64(const se3mpc_params* p, const se3mpc_controller_
                                 const double* spheres, int K, double obstacle_weight, const double* wind, long long wind_stride, double* time,
                                 double* pos, double* vel, double* att, double* omega, double* state, double* U, double* cost, double* trace,
                                 double* plan_last, double* clearance, void* stream);
+
+/* se3mpc_mppi_closed_loop_* around spheres that MOVE with constant velocity: the operands of se3mpc_mppi_closed_loop_*,
+ * and after `spheres` the sphere_vel [K][3] and sphere_t0 of se3mpc_mppi_moving_*.  sphere_t0 is the time of the RUN's start (cycle 0,
+ * simulator step 0) on the table's clock, the same in every chained call; the table advances with the run:
+ *   plan       cycle C = cycle_base + c, step k:   tau_k = sphere_t0 + plan_stamp, plan_stamp = (double)(C * substeps) * sim_dt + (double)k * dt
+ *              (the double the plan row's stamp is), the penalty then as in se3mpc_mppi_moving_*
+ *   clearance  simulator step s (0-based) of cycle C: the position the step produced against the centres at
+ *              tau = sphere_t0 + (double)(C * substeps + s + 1) * sim_dt; the form stays |pos - centre| - r with the raw radii
+ * each tau rounded to the kernel's type (tR) and centre_a = c_a + v_a * tR, so the advice of se3mpc_mppi_moving_* on small times holds.
+ * With sphere_vel = 0 every output equals se3mpc_mppi_closed_loop_*'s bit for bit.  Checks: those of se3mpc_mppi_closed_loop_*, then a
+ * non-finite sphere_t0: SE3MPC_ERR_PARAM; sphere_vel NULL with K > 0: SE3MPC_ERR_NULL.  K = 0 is allowed and reads neither table.  There is
+ * no staged or edge form. */
+int se3mpc_mppi_closed_loop_moving_f32(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B,
+                                       int cycles, int substeps, double sim_dt, uint32_t cycle_base, int shift, int S, int iters, double sigma,
+                                       double temperature, uint64_t seed, uint32_t iter_base, uint32_t index_base, const float* goal,
+                                       const float* spheres, const float* sphere_vel, double sphere_t0, int K, double obstacle_weight,
+                                       const float* wind, long long wind_stride, double* time, float* pos, float* vel, float* att, float* omega,
+                                       double* state, float* U, float* cost, float* trace, float* plan_last, float* clearance, void* stream);
+int se3mpc_mppi_closed_loop_moving_f64(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B,
+                                       int cycles, int substeps, double sim_dt, uint32_t cycle_base, int shift, int S, int iters, double sigma,
+                                       double temperature, uint64_t seed, uint32_t iter_base, uint32_t index_base, const double* goal,
+                                       const double* spheres, const double* sphere_vel, double sphere_t0, int K, double obstacle_weight,
+                                       const double* wind, long long wind_stride, double* time, double* pos, double* vel, double* att,
+                                       double* omega, double* state, double* U, double* cost, double* trace, double* plan_last,
+                                       double* clearance, void* stream);
 
 /* se3mpc_mppi_closed_loop_* with the reference's full edge loop per drone (edge/main_improved.py:96-152: plan -> TrajectorySmoother
  * (control/trajectory_smoother.py:115-213) -> GeometricController (control/geometric_controller.py:413-512) -> MotorMixer and motors

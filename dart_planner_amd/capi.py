@@ -377,6 +377,9 @@ _LOOP_TYPED_API = {
                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mppi_closed_loop_moving": [_PP, _CP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, _D, _I,
                                 _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mppi_closed_loop_swarm": [_PP, _CP, _SP, _I, _I, _I, _D, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P,
+                               _D, _I, _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
+    "swarm_separation": [_I, _I, _P, _P, _P, _P],
     "mppi_closed_loop_staged": [_PP, _CP, _SP, _MP, _XP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I,
                                 _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P],
     "mppi_closed_loop_edge": [_PP, _OP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _D, _P,
@@ -406,6 +409,7 @@ _PLAIN_API = {
     "se3mpc_key_cost": (C.c_float, [C.c_uint64]),
     "se3mpc_population_workspace": (C.c_int, [_I, _I]),
     "se3mpc_mppi_split_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "se3mpc_mppi_swarm_workspace_bytes": (C.c_size_t, [_I, _I]),
 }
 
 
@@ -502,6 +506,9 @@ class Library:
 
     def mppi_split_workspace_bytes(self, horizon: int, nprob: int, splits: int) -> int:
         return self._dll.se3mpc_mppi_split_workspace_bytes(horizon, nprob, splits)
+
+    def mppi_swarm_workspace_bytes(self, B: int, elem_size: int) -> int:
+        return self._dll.se3mpc_mppi_swarm_workspace_bytes(B, elem_size)
 
     def key_index(self, key: int) -> int:
         return self._dll.se3mpc_key_index(C.c_uint64(key))

@@ -328,6 +328,34 @@ class ClosedLoopMonteCarlo:
         logs = [dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"])] if log else []
         return self._result(st, sm, fl, logs=logs, U=U, cost=out["cost"], trace=out["trace"], clearance=out["clearance"])
 
+    def run_mppi_swarm(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float,
+                       temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None,
+                       nominal=None, log: bool = False, smoother=None, mixer=None, motor_health=None, sphere_velocities=None,
+                       sphere_t0: float = 0.0, swarm_size: int = 1, neighbours: int = 0, mate_radius: float = 0.0,
+                       want_neighbours: bool = False):
+        """:meth:`run_mppi_fused` for swarms (``se3mpc_mppi_closed_loop_swarm_*``): the B drones are B / `swarm_size` swarms
+        of `swarm_size` consecutive drones, and every drone plans around its `neighbours` nearest swarm-mates as spheres of radius
+        `mate_radius` that keep the velocity they have when the cycle starts (`obstacle_weight` weighs them like the shared `spheres`).
+        One call enqueues every cycle (one launch each, the drones' states handed over through a snapshot between launches), then
+        ``se3mpc_swarm_separation_*`` on the final state.  -> what :meth:`run_mppi_fused` returns (clearance: against the shared spheres
+        only), plus separation (B,) = the minimum over the cycle starts and the final state of the distance to the nearest mate, and
+        neighbours (B, `neighbours`) int32 = the mates chosen in the last cycle (None unless `want_neighbours`).  With swarm_size = 1 it is
+        :meth:`run_mppi_fused`, bit for bit.  There is no staged or edge form."""
+        self._no_smoother(smoother, "run_mppi_swarm")
+        self._no_mixer(mixer, motor_health, "run_mppi_swarm")
+        st, sm, fl = self._start(p0, v0)
+        U = self._mppi_start(p0, nominal)
+        sh = self.resolve_shift(substeps, sim_dt, shift)
+        out = self.ops.mppi_closed_loop_swarm(self.params, self.controller, self.simulator, st, *fl, goal, U, cycles, substeps, sim_dt,
+                                              n_samples, iters, sigma, temperature, swarm_size=swarm_size, neighbours=neighbours,
+                                              mate_radius=mate_radius, seed=seed, cycle_base=0, shift=sh, spheres=spheres,
+                                              obstacle_weight=obstacle_weight, wind=wind, want_plan=log, sphere_vel=sphere_velocities,
+                                              sphere_t0=sphere_t0, want_neighbours=want_neighbours)
+        sep = self.ops.swarm_separation(fl[1], fl[2], swarm_size, separation=out["separation"])
+        logs = [dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"])] if log else []
+        return self._result(st, sm, fl, logs=logs, U=U, cost=out["cost"], trace=out["trace"], clearance=out["clearance"], separation=sep,
+                            neighbours=out["neighbours"])
+
     def run_mppi_fused_staged(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float,
                               temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None,
                               shift: Optional[int] = None, nominal=None, log: bool = False, smoother: Optional[SmootherParams] = None,

@@ -791,6 +791,94 @@ class Ops:
             trace = trace[:, :max(int(cycles), 0), :max(int(iters), 0)]
         return dict(U=U, cost=cost, trace=trace, plan_last=plan, clearance=clearance)
 
+    def mppi_swarm_workspace(self, B: int, suf: str):
+        """A workspace for :meth:`mppi_closed_loop_swarm` over `B` drones of dtype `suf` ("f32" / "f64"): the two snapshot images (no
+        initialisation needed)."""
+        esz = {"f32": 4, "f64": 8}[suf]
+        return self.be.empty((max(self.lib.mppi_swarm_workspace_bytes(int(B), esz) // esz, 1),), suf)
+
+    def mppi_closed_loop_swarm(self, params: Params, cp: ControllerParams, sp: SimulatorParams, state, time, pos, vel, att, omega, goal, U,
+                               cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
+                               swarm_size: int = 1, neighbours: int = 0, mate_radius: float = 0.0, seed: int = 0, cycle_base: int = 0,
+                               shift: int = 1, iter_base: int = 0, index_base: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None,
+                               want_trace: bool = True, want_plan: bool = False, clearance=None, want_clearance: bool = True, sphere_vel=None,
+                               sphere_t0: float = 0.0, separation=None, want_neighbours: bool = False, workspace=None):
+        """se3mpc_mppi_closed_loop_swarm_*: :meth:`mppi_closed_loop` around moving spheres for B / `swarm_size` swarms of `swarm_size`
+        drones, every drone planning around its `neighbours` nearest swarm-mates as spheres of radius `mate_radius` that fly on with the
+        velocity they have when the cycle starts; one launch per cycle plus a seed, all enqueued by one call.  spheres / sphere_vel: the
+        shared table (K, 4) / (K, 3) (sphere_vel None: the spheres stand still).  separation: a (B,) running minimum to continue, or None: a
+        fresh one at +inf; it takes the distance to the nearest mate at every cycle's start (:meth:`swarm_separation` adds the state as it
+        stands).  workspace: a tensor of :meth:`mppi_swarm_workspace` to reuse (required under graph capture); None allocates one.
+        -> the dict of :meth:`mppi_closed_loop` plus separation (B,) and neighbours (B, `neighbours`) int32 | None: the drones chosen in
+        the last cycle, rank order, -1 in unused slots."""
+        B = pos.shape[0]
+        suf = self.be.suffix(pos)
+        N = params.horizon
+        self._drone_state(B, suf, pos, vel, att, omega, goal=goal)
+        self._ctrl_state(state, B)
+        self._clock(time, B, "time")
+        self.be.check(U, "U")
+        if tuple(U.shape) != (B, N, 3) or self.be.suffix(U) != suf:
+            raise ValueError(f"U: expected ({B}, {N}, 3) {suf}, got {tuple(U.shape)}")
+        w_stride = self._wind(wind, B, suf)
+        K = 0
+        if spheres is not None:
+            K = self._spheres(spheres, suf)
+        if sphere_vel is None and K:
+            sphere_vel = self.be.empty((K, 3), suf)
+            sphere_vel[...] = 0.0
+        motion = self._sphere_vel(sphere_vel, sphere_t0, K, suf) if K else (None, float(sphere_t0))
+        self._per_drone(B, suf, clearance=clearance, separation=separation)
+        if clearance is None and want_clearance and K:
+            clearance = self.be.empty((B,), suf)
+            clearance[...] = float("inf")
+        if separation is None:
+            separation = self.be.empty((B,), suf)
+            separation[...] = float("inf")
+        Kn = int(neighbours)
+        esz = {"f32": 4, "f64": 8}[suf]
+        if workspace is None:
+            workspace = self.mppi_swarm_workspace(B, suf)
+        else:
+            self.be.check(workspace, "workspace")
+            if self.be.suffix(workspace) != suf:
+                raise ValueError(f"workspace: expected {suf}")
+        cost = self.be.empty((B,), suf)
+        trace = self.be.empty((B, max(int(cycles), 1), max(int(iters), 1)), suf) if want_trace else None
+        plan = self.be.empty((B, 3, N, 3), suf) if want_plan else None
+        nb = self.be.empty((B, max(Kn, 1)), "i32") if want_neighbours else None
+        if nb is not None:
+            nb[...] = -1
+        self.lib.loop_call("mppi_closed_loop_swarm", suf, params, cp, sp, B, int(swarm_size), Kn, float(mate_radius), int(cycles), int(substeps),
+                           float(sim_dt), int(cycle_base) & 0xFFFFFFFF, int(shift), int(n_samples), int(iters), float(sigma), float(temperature),
+                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(iter_base) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF, self.be.ptr(goal),
+                           self.be.ptr(spheres if K else None), *motion, K, float(obstacle_weight), self.be.ptr(wind), w_stride, self.be.ptr(time),
+                           self.be.ptr(pos), self.be.ptr(vel), self.be.ptr(att), self.be.ptr(omega), self.be.ptr(state), self.be.ptr(U),
+                           self.be.ptr(cost), self.be.ptr(trace), self.be.ptr(plan), self.be.ptr(clearance), self.be.ptr(separation),
+                           self.be.ptr(nb), self.be.ptr(workspace), int(workspace.numel()) * esz, self.be.stream())
+        if trace is not None and (cycles <= 0 or iters <= 0):
+            trace = trace[:, :max(int(cycles), 0), :max(int(iters), 0)]
+        if nb is not None:
+            nb = nb[:, :max(Kn, 0)]
+        return dict(U=U, cost=cost, trace=trace, plan_last=plan, clearance=clearance, separation=separation, neighbours=nb)
+
+    def swarm_separation(self, pos, vel, swarm_size: int, separation=None):
+        """se3mpc_swarm_separation_*: separation[b] = min(separation[b], the distance of drone b to its nearest swarm-mate with a finite
+        (pos, vel)) on pos, vel (B, 3) as they stand, swarms of `swarm_size` consecutive drones.  separation None: a fresh (B,) at +inf.
+        -> separation."""
+        B = pos.shape[0]
+        suf = self.be.suffix(pos)
+        for nm, a in (("pos", pos), ("vel", vel)):
+            self.be.check(a, nm)
+            if tuple(a.shape) != (B, 3) or self.be.suffix(a) != suf:
+                raise ValueError(f"{nm}: expected ({B}, 3) {suf}, got {tuple(a.shape)}")
+        self._per_drone(B, suf, separation=separation)
+        if separation is None:
+            separation = self.be.empty((B,), suf)
+            separation[...] = float("inf")
+        self.lib.loop_call("swarm_separation", suf, B, int(swarm_size), self.be.ptr(pos), self.be.ptr(vel), self.be.ptr(separation), self.be.stream())
+        return separation
+
     def mppi_closed_loop_staged(self, params: Params, cp: ControllerParams, sp: SimulatorParams, state, time, pos, vel, att, omega, goal, U,
                                 cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
                                 seed: int = 0, cycle_base: int = 0, shift: int = 1, iter_base: int = 0, index_base: int = 0, spheres=None,

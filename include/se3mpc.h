@@ -40,6 +40,7 @@ extern "C" {
 #define SE3MPC_MAX_HORIZON 64      /* 9*N <= 576 decision variables per problem            */
 #define SE3MPC_MAX_CORRECTIONS 10  /* L-BFGS memory m (SciPy default maxcor = 10)          */
 #define SE3MPC_MAX_SPHERES 256     /* obstacle table staged in LDS (4 KB)                  */
+#define SE3MPC_MAX_SWARM 1024      /* drones per swarm (se3mpc_mppi_closed_loop_swarm_*)   */
 
 enum se3mpc_status {
   SE3MPC_OK = 0,
@@ -981,6 +982,71 @@ int se3mpc_mppi_closed_loop_moving_f64(const se3mpc_params* p, const se3mpc_cont
                                        const double* wind, long long wind_stride, double* time, double* pos, double* vel, double* att,
                                        double* omega, double* state, double* U, double* cost, double* trace, double* plan_last,
                                        double* clearance, void* stream);
+
+/* se3mpc_mppi_closed_loop_moving_* for SWARMS: the B drones of a call are B / swarm_size swarms of M = swarm_size drones
+ * (drone b belongs to swarm b / M; its mates are the other drones of that swarm), and every drone plans around its nearest mates as
+ * spheres of radius mate_radius that move with constant velocity.  The operands are those of se3mpc_mppi_closed_loop_moving_*, same
+ * order and meaning, with K = the rows of the SHARED table (spheres, sphere_vel) every drone sees; in front of them swarm_size,
+ * neighbours_k = Kn and mate_radius, behind them separation, neighbours and the workspace.  One planning cycle is one launch (one
+ * workgroup of min(S, 256) lanes per drone), a call with cycles = C enqueues C + 1 launches on the stream (a seed and the cycles),
+ * allocates nothing and synchronises nothing.  Cycle C = cycle_base + c of drone b:
+ *   snapshot   (pos, vel) of every drone as they stand when the cycle starts ([B][6] in the workspace, written by the launch before)
+ *   d2         for mate i of the drone, in float64 without contraction, summed left to right:  d2_i = dx*dx + dy*dy + dz*dz,
+ *              dx = (double)snap_pos[i].x - (double)own.x and likewise y and z, own = the drone's own snapshot row
+ *   eligible   a mate whose six snapshot values are finite; E = their number (E = 0 when the drone's own row is not finite)
+ *   selection  the Kn_eff = min(Kn, E) eligible mates with the smallest (d2, drone index): equal d2 resolves to the lower index
+ *   table      rows [0, K) the shared spheres; row K + r the mate a of rank r: velocity vel_a, radius mate_radius (so the penalty sees
+ *              (mate_radius + margin)^2 by the expression of the shared rows), centre c'_a = pos_a - (vel_a * tR0), two roundings in the
+ *              entry point's type without contraction, tR0 = (R)(sphere_t0 + (double)(C * substeps) * sim_dt): the time of the cycle's
+ *              start on the table's clock, so centre = c' + v * tR_k puts the mate where it is at the cycle's start and extrapolates it
+ *              along the horizon
+ *   plan ... warm start   the cycle of se3mpc_mppi_closed_loop_moving_* on that table of K + Kn_eff rows; the in-flight clearance is
+ *              measured against rows [0, K) only (the mates' extrapolated positions are predictions)
+ * separation [B]: in / out, normally +inf: separation[b] = min(separation[b], (R)sqrt(min over the eligible mates of d2)) at every
+ * cycle's start, on the snapshot: the true distance at the cycle boundaries; untouched when E = 0.  se3mpc_swarm_separation_* folds in
+ * the same quantity of (pos, vel) as they stand (call it after the last cycle, so that the final positions count).  neighbours: NULL or
+ * [B][Kn] int32: the drones chosen in the call's last cycle, as indices into the call's B drones in rank order, -1 in unused slots.
+ * workspace: device memory of at least se3mpc_mppi_swarm_workspace_bytes(B, sizeof(R)) bytes = two [B][6] images, aligned to R; it
+ * needs no initialisation and carries nothing from call to call.  Guarantees:
+ *   reduces to the moving loop   with swarm_size = 1 or neighbours_k = 0 every output shared with se3mpc_mppi_closed_loop_moving_*
+ *                                equals that entry point's, bit for bit
+ *   continuation                 one call with cycles = C equals C calls with cycles = 1 and cycle_base = 0 .. C - 1, bit for bit,
+ *                                separation and the neighbours of the last cycle included
+ *   trace layout                 trace stays [B][cycles][iters]
+ *   schedule independence        every workgroup reads one image of the snapshot and writes the other, the images swap between launches
+ *                                and the kernel boundary is the only synchronisation (no atomics, no flags): results are identical run
+ *                                to run and do not depend on how the device schedules workgroups
+ * Argument rules: everything se3mpc_mppi_closed_loop_moving_* rejects, with the same codes; swarm_size outside [1, SE3MPC_MAX_SWARM],
+ * B not a multiple of swarm_size, neighbours_k < 0, K + neighbours_k > SE3MPC_MAX_SPHERES, workspace_bytes too small (swarm_size > 1,
+ * workspace given): SE3MPC_ERR_SHAPE; mate_radius negative or not finite: SE3MPC_ERR_PARAM; a NULL workspace or a NULL separation
+ * when swarm_size > 1, neighbours_k > 0, B > 0 and cycles > 0: SE3MPC_ERR_NULL.  (With neighbours_k = 0 the snapshot serves the
+ * separation alone: a NULL workspace or separation then leaves separation untouched.)  se3mpc_mppi_swarm_workspace_bytes returns 0
+ * for arguments outside these rules (B < 0, elem_size not 4 or 8).  Every rejected call sets se3mpc_last_error and launches nothing.
+ * There is no staged or edge form. */
+size_t se3mpc_mppi_swarm_workspace_bytes(int B, int elem_size);
+int se3mpc_mppi_closed_loop_swarm_f32(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B,
+                                      int swarm_size, int neighbours_k, double mate_radius, int cycles, int substeps, double sim_dt,
+                                      uint32_t cycle_base, int shift, int S, int iters, double sigma, double temperature, uint64_t seed,
+                                      uint32_t iter_base, uint32_t index_base, const float* goal, const float* spheres, const float* sphere_vel,
+                                      double sphere_t0, int K, double obstacle_weight, const float* wind, long long wind_stride, double* time,
+                                      float* pos, float* vel, float* att, float* omega, double* state, float* U, float* cost, float* trace,
+                                      float* plan_last, float* clearance, float* separation, int32_t* neighbours, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+int se3mpc_mppi_closed_loop_swarm_f64(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B,
+                                      int swarm_size, int neighbours_k, double mate_radius, int cycles, int substeps, double sim_dt,
+                                      uint32_t cycle_base, int shift, int S, int iters, double sigma, double temperature, uint64_t seed,
+                                      uint32_t iter_base, uint32_t index_base, const double* goal, const double* spheres,
+                                      const double* sphere_vel, double sphere_t0, int K, double obstacle_weight, const double* wind,
+                                      long long wind_stride, double* time, double* pos, double* vel, double* att, double* omega, double* state,
+                                      double* U, double* cost, double* trace, double* plan_last, double* clearance, double* separation,
+                                      int32_t* neighbours, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The distance of every drone to its nearest eligible swarm-mate as (pos, vel) [B][3] stand: separation[b] = min(separation[b],
+ * (R)sqrt(min d2)) with d2, eligibility and the E = 0 rule of se3mpc_mppi_closed_loop_swarm_*.  Reads pos and vel, writes separation only.
+ * swarm_size outside [1, SE3MPC_MAX_SWARM], B < 0 or not a multiple of swarm_size: SE3MPC_ERR_SHAPE; a NULL operand with B > 0:
+ * SE3MPC_ERR_NULL.  swarm_size = 1 and B = 0 are no-ops. */
+int se3mpc_swarm_separation_f32(int B, int swarm_size, const float* pos, const float* vel, float* separation, void* stream);
+int se3mpc_swarm_separation_f64(int B, int swarm_size, const double* pos, const double* vel, double* separation, void* stream);
 
 /* se3mpc_mppi_closed_loop_* with the reference's full edge loop per drone (edge/main_improved.py:96-152: plan -> TrajectorySmoother
  * (control/trajectory_smoother.py:115-213) -> GeometricController (control/geometric_controller.py:413-512) -> MotorMixer and motors

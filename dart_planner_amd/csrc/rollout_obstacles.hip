@@ -69,15 +69,17 @@ __device__ __forceinline__ void obstacle_sweep(const R* __restrict__ tile, const
 }
 
 // The same residuals on the matrix core (float32).  |P_k - c_j|^2 - R_j^2 = |P_k|^2 - 2 P_k.c_j + (|c_j|^2 - R_j^2) is a K = 4 contraction of
-// (P_k, |P_k|^2) with (-2 c_j, 1) plus a per-sphere constant: ONE v_mfma_f32_16x16x4_f32 forms the residuals of 16 spheres x 16 trajectories at a
+// (P_k, |P_k|^2) with (-2 c_j, 1) plus a per-sphere constant (P_k and c_j both taken about the table's mean centre, see obstacle_sweep_mfma): ONE v_mfma_f32_16x16x4_f32 forms the residuals of 16 spheres x 16 trajectories at a
 // step, the constant riding in as the accumulator input.  A = the sphere chunk (one register per 16 spheres, loop-invariant), C-in = four
 // constants per lane, B = a row of the position tile exactly as the forward sweep stored it ([axis][k][trajectory]: lanes 0-47 read x / y / z of
 // 16 consecutive trajectories, lanes 48-63 the |P_k|^2 row this wavefront has just written behind the three axes) -- no transposed image.
 // What is left for the VALU is the fold: two v_min3 and the violation sum per four residuals, running per lane = (trajectory l % 16 of the block,
 // spheres 4 (l / 16) ... + 3) across all steps; the four lane groups meet once at the end (obstacle_mfma_fold).  Against the packed-VALU sweep
 // (10 instructions per sphere pair) this issues 8 VALU instructions + 1 MFMA per 64 residuals-per-16-lanes, i.e. 2.25 instead of 5 per residual
-// and lane, and the multiplies run beside them on the matrix pipe.  Price: the expanded form cancels, |P|^2 ~ 1e3 m^2 against a residual
-// near 0 at an obstacle's surface: float32 absolute error ~ 5e-5 m^2 there (1e-5 m of distance at R = 2.5 m) where the difference form had 1e-6.
+// and lane, and the multiplies run beside them on the matrix pipe.  Price: the expanded form cancels, |P - o|^2 + |c - o|^2 (a few 1e2 m^2 for a
+// table 15 m across) against a residual near 0 at an obstacle's surface: float32 absolute error ~ 2e-5 m^2 there where the difference form had
+// 1e-6.  (Taken about the world's origin the same cancellation grew with the scene's distance from it: 2.4e-4 on a violation of 4.8 m^2 with
+// positions 20 m out, past the suite's bound on the violation once a small safety margin made the violations shallow.)
 // MEASURED (MI355X, profiles/r03g_cfg3_mfma_vs_valu.txt): 64 x 8192 x horizon 50 x 16 spheres 163.4 us against 166.0 us for the packed-VALU sweep,
 // 1 M rollouts 330 against 336 us, the bench's ring of batches 164.4 against 161.9 us, one 8192-rollout launch 8.74 against 8.43 us -- the
 // kernel is bound by its load latency at two workgroups per CU, not by VALU issue (64 % busy), so halving the evaluation's instructions buys
@@ -96,26 +98,34 @@ __device__ __forceinline__ void obstacle_mfma_init(ObsMfmaAcc& acc) {
 #pragma unroll
   for (int tb = 0; tb < 4; ++tb) { acc.mn[tb] = INFINITY; acc.vs[tb] = obs_f2{0.0f, 0.0f}; }
 }
-__device__ __forceinline__ void obstacle_sweep_mfma(float* __restrict__ tile, const float* __restrict__ sph, int Nn, int Kpad, int kbeg, int kend,
-                                                    int kstep, int lane, ObsMfmaAcc& acc) {
+__device__ __forceinline__ void obstacle_sweep_mfma(float* __restrict__ tile, const float* __restrict__ sph, int Nn, int K, int Kpad, int kbeg,
+                                                    int kend, int kstep, int lane, ObsMfmaAcc& acc) {
   const int li = lane & 15, lk = lane >> 4;
-  if (Kpad <= 0) return;
-  float* pprow = tile + (size_t)3 * Nn * kWave;                                    // [Nn][64]: |P_k|^2, the tile's fourth "axis"
+  if (Kpad <= 0 || K <= 0) return;
+  float* pprow = tile + (size_t)3 * Nn * kWave;                                    // [Nn][64]: |P_k - o|^2, the tile's fourth "axis"
+  // The expanded form cancels in proportion to |P|^2 + |c|^2, and |P - c| does not depend on the origin: positions and centres are taken
+  // about o = the mean of the table's centres (padding rows are (0, 0, 0); every lane forms the same sums in the same order), so that what
+  // cancels next to an obstacle is the table's own extent, not its distance from the world's origin.
+  float ox = 0.0f, oy = 0.0f, oz = 0.0f;
+  for (int j = 0; j < Kpad; ++j) { ox += sph[4 * j + 0]; oy += sph[4 * j + 1]; oz += sph[4 * j + 2]; }
+  { const float inv = 1.0f / (float)K; ox *= inv; oy *= inv; oz *= inv; }
+  const float ob = lk == 0 ? ox : (lk == 1 ? oy : (lk == 2 ? oz : 0.0f));         // this lane group's component of o (the |P - o|^2 row: none)
   // this wavefront owns steps kbeg, kbeg + kstep, ...: their |P_k|^2 rows first (read back across lanes below)
   for (int k = kbeg; k < kend; k += kstep) {
-    const float px = tile[((size_t)0 * Nn + k) * kWave + lane], py = tile[((size_t)1 * Nn + k) * kWave + lane],
-                pz = tile[((size_t)2 * Nn + k) * kWave + lane];
+    const float px = tile[((size_t)0 * Nn + k) * kWave + lane] - ox, py = tile[((size_t)1 * Nn + k) * kWave + lane] - oy,
+                pz = tile[((size_t)2 * Nn + k) * kWave + lane] - oz;
     pprow[(size_t)k * kWave + lane] = px * px + (py * py + pz * pz);
   }
   group_sync<kWave>();
   for (int j0 = 0; j0 < Kpad; j0 += 16) {
     const float* sa = sph + 4 * (j0 + li);
-    const float a = lk < 3 ? -2.0f * sa[lk] : 1.0f;                                // A[sphere li][component lk]
+    const float a = lk < 3 ? -2.0f * (sa[lk] - ob) : 1.0f;                         // A[sphere li][component lk]
     vf4 w;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float* sw = sph + 4 * (j0 + 4 * lk + r);
-      w[r] = (sw[0] * sw[0] + (sw[1] * sw[1] + sw[2] * sw[2])) - sw[3];           // |c|^2 - R^2; a padding row (0, 0, 0, -inf) gives +inf
+      const float cx = sw[0] - ox, cy = sw[1] - oy, cz = sw[2] - oz;
+      w[r] = (cx * cx + (cy * cy + cz * cz)) - sw[3];                             // |c - o|^2 - R^2; a padding row (0, 0, 0, -inf) gives +inf
     }
 #pragma unroll 2
     for (int k = kbeg; k < kend; k += kstep) {
@@ -124,7 +134,7 @@ __device__ __forceinline__ void obstacle_sweep_mfma(float* __restrict__ tile, co
       float b[4];
       vf4 d[4];
 #pragma unroll
-      for (int tb = 0; tb < 4; ++tb) b[tb] = brow[16 * tb];
+      for (int tb = 0; tb < 4; ++tb) b[tb] = brow[16 * tb] - ob;
 #pragma unroll
       for (int tb = 0; tb < 4; ++tb) d[tb] = mfma_16x16x4_f32(a, b[tb], w);
 #pragma unroll
@@ -248,7 +258,7 @@ rollout_obstacles_kernel(DevParams<R> q, int B, int ld, const R* __restrict__ p0
     if constexpr (MF) {
       ObsMfmaAcc acc;
       obstacle_mfma_init(acc);
-      obstacle_sweep_mfma(tile, sph, Nn, Kpad, a, Nn, W, lane, acc);
+      obstacle_sweep_mfma(tile, sph, Nn, K, Kpad, a, Nn, W, lane, acc);
       obstacle_mfma_fold(acc, lane, mn, vs);
     } else {
       obstacle_sweep<R>(tile, sph, Nn, Kpad, a, Nn, W, lane, mn, vs);
@@ -262,8 +272,8 @@ rollout_obstacles_kernel(DevParams<R> q, int B, int ld, const R* __restrict__ p0
     if constexpr (MF) {
       ObsMfmaAcc acc;
       obstacle_mfma_init(acc);
-      if (a >= 3) obstacle_sweep_mfma(tile, sph, Nn, Kpad, a - 3, kh, NH, lane, acc);
-      obstacle_sweep_mfma(tile, sph, Nn, Kpad, kh + a, Nn, W, lane, acc);
+      if (a >= 3) obstacle_sweep_mfma(tile, sph, Nn, K, Kpad, a - 3, kh, NH, lane, acc);
+      obstacle_sweep_mfma(tile, sph, Nn, K, Kpad, kh + a, Nn, W, lane, acc);
       obstacle_mfma_fold(acc, lane, mn, vs);
     } else {
       if (a >= 3) obstacle_sweep<R>(tile, sph, Nn, Kpad, a - 3, kh, NH, lane, mn, vs);

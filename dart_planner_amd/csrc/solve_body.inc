@@ -701,7 +701,8 @@
       for (int j = 0; j < J; ++j) { differs = differs | !(x[j] == xo[j]); x[j] = xo[j]; g[j] = grad_of(j, xo[j]); }     // (g was not touched by the search: this is what it holds already, bit for bit)
       if (group_ballot<G>(differs) != 0ull) x_is_last = false;
       f = fold;
-      if (col == 0) { task = SE3MPC_TASK_ABNORMAL; status = 2; break; }
+      // (SciPy reports a stop past one of its limits as status 1 whatever the task says: warnflag = 1 when nfev > maxfun or nit >= maxiter)
+      if (col == 0) { task = SE3MPC_TASK_ABNORMAL; status = (nfev > q.maxfun || nit >= q.maxiter) ? 1 : 2; break; }
       col = 0; theta = 1.0; iupdat = 0;
       continue;
     }

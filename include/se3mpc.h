@@ -84,7 +84,9 @@ typedef struct se3mpc_params {
 
 /* Per-problem result of the solver, mirroring scipy's OptimizeResult fields the reference
  * reads (planner.py:271-278): status 0 = converged, 1 = iteration/evaluation limit,
- * 2 = abnormal termination in line search.  `task` is the L-BFGS-B stop reason. */
+ * 2 = abnormal termination in line search.  `task` is the L-BFGS-B stop reason.  As in SciPy
+ * the limits win: a line search that ends abnormally after nfev has passed max_fun (or nit has
+ * reached max_iterations) reports status 1 with task SE3MPC_TASK_ABNORMAL. */
 typedef struct se3mpc_solve_info {
   double fun;        /* f at the returned x                                              */
   int32_t nit;       /* iterations                                                       */

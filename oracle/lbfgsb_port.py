@@ -671,7 +671,8 @@ def minimize(fun_and_grad: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0,
             # restore the previous iterate
             x, g, f = t_x, r_g, fold
             if S.col == 0:
-                return Result(x, f, nit, nfev, 2, "ABNORMAL_TERMINATION_IN_LNSRCH", tr)
+                # SciPy's driver: warnflag = 1 whenever nfev > maxfun or nit >= maxiter, whatever the task; 2 otherwise
+                return Result(x, f, nit, nfev, 1 if (nfev > maxfun or nit >= maxiter) else 2, "ABNORMAL_TERMINATION_IN_LNSRCH", tr)
             S.reset_memory()
             continue
         # ---------------- new iterate

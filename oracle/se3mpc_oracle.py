@@ -47,6 +47,10 @@ class OracleConfig:
     mass: float = 1.5
     gravity: float = 9.81
     position_bound: float = 100.0      # planner.py:383-384
+    terminal_factor: float = 10.0      # planner.py:548 (a literal there)
+    max_corrections: int = 10          # SciPy's maxcor default (planner.py:256-268 does not set it)
+    max_linesearch: int = 20           # SciPy's maxls default
+    max_fun: int = 15000               # SciPy's maxfun default
 
     @property
     def hover_thrust(self) -> float:   # planner.py:151
@@ -142,7 +146,7 @@ def objective(x, goal, cfg: OracleConfig):
     cost = cost + cfg.acceleration_weight * np.sum(acc ** 2, axis=(-1, -2))
     cost = cost + cfg.thrust_weight * np.sum((T - cfg.hover_thrust * e3) ** 2, axis=(-1, -2))
     if goal is not None:
-        cost = cost + 10 * cfg.position_weight * np.sum((P[..., -1, :] - np.asarray(goal, float)) ** 2, axis=-1)
+        cost = cost + cfg.terminal_factor * cfg.position_weight * np.sum((P[..., -1, :] - np.asarray(goal, float)) ** 2, axis=-1)
     return cost
 
 
@@ -179,7 +183,7 @@ def objective_loops(x, goal, cfg: OracleConfig) -> float:
         cost += cfg.thrust_weight * np.sum(d ** 2)
     if goal is not None:
         e = P[-1] - goal
-        cost += 10 * cfg.position_weight * np.sum(e ** 2)
+        cost += cfg.terminal_factor * cfg.position_weight * np.sum(e ** 2)
     return cost
 
 
@@ -202,7 +206,7 @@ def objective_ordered(x, goal, cfg: OracleConfig) -> float:
     d = T - np.array([0, 0, cfg.hover_thrust])
     terms.append(cfg.thrust_weight * np.sum(d ** 2, axis=-1))
     if goal is not None:
-        terms.append(np.atleast_1d(10 * cfg.position_weight * np.sum((P[-1] - g) ** 2)))
+        terms.append(np.atleast_1d(cfg.terminal_factor * cfg.position_weight * np.sum((P[-1] - g) ** 2)))
     return float(np.cumsum(np.concatenate(terms))[-1])
 
 
@@ -321,7 +325,8 @@ def solve(p0, v0, goal, cfg: OracleConfig, x0: Optional[np.ndarray] = None):
     res = minimize(fun=lambda x: objective_ordered(x, g_, cfg), x0=x0, method="L-BFGS-B",
                    jac=lambda x: gradient(x, g_, cfg), bounds=[(lo, hi) for lo, hi in b],
                    options={"maxiter": cfg.max_iterations, "gtol": cfg.convergence_tolerance,
-                            "ftol": cfg.convergence_tolerance * 10, "disp": False})
+                            "ftol": cfg.convergence_tolerance * 10, "maxcor": cfg.max_corrections,
+                            "maxls": cfg.max_linesearch, "maxfun": cfg.max_fun, "disp": False})
     return np.asarray(res.x, float), dict(nit=int(res.nit), nfev=int(res.nfev), status=int(res.status),
                                           fun=float(res.fun), success=bool(res.success), message=str(res.message))
 
@@ -348,7 +353,8 @@ def plan_reference_shaped(p0, v0, goal, cfg: OracleConfig):
     res = minimize(fun=lambda x: objective_loops(x, g_, cfg), x0=x0, method="L-BFGS-B",
                    jac=lambda x: gradient_loops(x, g_, cfg), bounds=[(lo, hi) for lo, hi in b],
                    options={"maxiter": cfg.max_iterations, "gtol": cfg.convergence_tolerance,
-                            "ftol": cfg.convergence_tolerance * 10, "disp": False})
+                            "ftol": cfg.convergence_tolerance * 10, "maxcor": cfg.max_corrections,
+                            "maxls": cfg.max_linesearch, "maxfun": cfg.max_fun, "disp": False})
     return extract_solution(res.x, cfg)
 
 
@@ -410,7 +416,7 @@ def rollout_cost_grad(p0, v0, goal, T, cfg: OracleConfig):
     A = T / m - cfg.gravity * e3
     wp, wv, wa, wT = cfg.position_weight, cfg.velocity_weight, cfg.acceleration_weight, cfg.thrust_weight
     G = 2 * wa * A / m + 2 * wT * (T - cfg.hover_thrust * e3)
-    lamP = 2 * wp * 11.0 * (P[..., N - 1, :] - goal)
+    lamP = 2 * wp * (1 + cfg.terminal_factor) * (P[..., N - 1, :] - goal)
     lamV = 2 * wv * V[..., N - 1, :]
     for k in range(N - 2, -1, -1):
         G[..., k, :] += (0.5 * dt * dt * lamP + dt * lamV) / m

@@ -28,9 +28,10 @@ def scene(B):
     return p0, v0, goal, wind
 
 
-def _operands(h, N, B, wind):
+def _operands(h, N, B, wind, blocks=None):
+    """blocks: dict(prm, sp, op) of parameter structs in place of the defaults (tests/param_sets.loop_blocks)."""
     p0, v0, goal, w = (h.prob(a) for a in scene(B))
-    mc = ClosedLoopMonteCarlo(h.ops, Params.reference_defaults(horizon=N))
+    mc = ClosedLoopMonteCarlo(h.ops, Params.reference_defaults(horizon=N)) if blocks is None else ClosedLoopMonteCarlo(h.ops, blocks["prm"], blocks["cp"], blocks["sp"])
     return mc, (p0, v0, goal), {"rows": w, None: None, "shared": w[0].contiguous()}[wind]
 
 
@@ -44,12 +45,12 @@ def _host(h, out, depth):
 _chain = {}
 
 
-def chain(h, N, B, depth, substeps, wind="rows", cycles=CYCLES):
+def chain(h, N, B, depth, substeps, wind="rows", cycles=CYCLES, blocks=None):
     """ClosedLoopMonteCarlo.run_edge for the configuration, as host arrays (computed once, never written)."""
-    key = (id(h.ops), np.dtype(h.dt).name, N, B, depth, substeps, wind, cycles)
+    key = (id(h.ops), np.dtype(h.dt).name, N, B, depth, substeps, wind, cycles, blocks is not None)
     if key not in _chain:
-        mc, args, w = _operands(h, N, B, wind)
-        res = _host(h, mc.run_edge(*args, cycles, substeps, SIM_DT, latency_depth=depth, wind=w), depth)
+        mc, args, w = _operands(h, N, B, wind, blocks)
+        res = _host(h, mc.run_edge(*args, cycles, substeps, SIM_DT, latency_depth=depth, wind=w, onboard=None if blocks is None else blocks["op"]), depth)
         for v in res.values():
             v.setflags(write=False)
         _chain[key] = res
@@ -68,12 +69,13 @@ def same_run(got, ref, what):
         same_bits(got[key], ref[key], f"{what}: {key}")
 
 
-def check_equals_chain(h, N, B, depth, substeps, wind="rows", last_plan=False):
+def check_equals_chain(h, N, B, depth, substeps, wind="rows", last_plan=False, cycles=CYCLES, blocks=None):
     """run_edge_fused gives the bytes of run_edge: the drones' state, the clocks, the onboard records, the counters and -- with a buffer -- the
     latency records and the whole ring; with `last_plan` also the last cycle's plan = a solve from the chain's state after CYCLES - 1 cycles."""
-    ref = chain(h, N, B, depth, substeps, wind)
-    mc, args, w = _operands(h, N, B, wind)
-    got = mc.run_edge_fused(*args, CYCLES, substeps, SIM_DT, latency_depth=depth, wind=w, want_last_plan=last_plan)
+    ref = chain(h, N, B, depth, substeps, wind, cycles, blocks)
+    mc, args, w = _operands(h, N, B, wind, blocks)
+    got = mc.run_edge_fused(*args, cycles, substeps, SIM_DT, latency_depth=depth, wind=w, want_last_plan=last_plan,
+                            onboard=None if blocks is None else blocks["op"])
     assert got["logs"] == [] and got["latency"]["depth"] == depth and "controller_state" not in got
     same_run(_host(h, got, depth), ref, f"N={N} B={B} depth={depth} substeps={substeps} wind={wind}")
     if not last_plan:
@@ -81,7 +83,7 @@ def check_equals_chain(h, N, B, depth, substeps, wind="rows", last_plan=False):
         return
     x = h.to_host(got["last_plan"]["x"])
     assert x.shape == (B, 9 * N)
-    before = chain(h, N, B, depth, substeps, wind, cycles=CYCLES - 1)
+    before = chain(h, N, B, depth, substeps, wind, cycles - 1, blocks)
     sol = h.ops.solve(mc.params, h.to_dev(before["pos"].copy()), h.to_dev(before["vel"].copy()), args[2], want_trajectory="accelerations")
     same_bits(x, h.to_host(sol["x"]), "last_plan x")
     same_bits(h.to_host(got["last_plan"]["accelerations"]), h.to_host(sol["accelerations"]), "last_plan accelerations")

@@ -29,14 +29,15 @@ def scene(B):
     return p0, v0, goal, wind, health
 
 
-def _operands(h, N, B, stage, wind, smoother):
-    """-> (mc, positional arguments, keyword arguments) of run / run_fused_staged for one configuration."""
+def _operands(h, N, B, stage, wind, smoother, blocks=None):
+    """-> (mc, positional arguments, keyword arguments) of run / run_fused_staged for one configuration.
+    blocks: dict(prm, cp, sp, mixer) of parameter structs in place of the defaults (tests/param_sets.loop_blocks)."""
     p0, v0, goal, w, hl = (h.prob(a) for a in scene(B))
     with_smoother, with_mixer, health = STAGES[stage] if stage is not None else (False, False, None)
-    mc = ClosedLoopMonteCarlo(h.ops, Params.reference_defaults(horizon=N))
+    mc = ClosedLoopMonteCarlo(h.ops, Params.reference_defaults(horizon=N)) if blocks is None else ClosedLoopMonteCarlo(h.ops, blocks["prm"], blocks["cp"], blocks["sp"])
     kw = dict(wind={"rows": w, None: None, "shared": w[0].contiguous()}[wind],
               smoother=SmootherParams.reference_defaults(**SMOOTHERS[smoother]) if with_smoother else None,
-              mixer=h.ops.lib.mixer_default_params() if with_mixer else None,
+              mixer=(h.ops.lib.mixer_default_params() if blocks is None else blocks["mixer"]) if with_mixer else None,
               motor_health={"rows": hl, None: None, "shared": hl[0].contiguous()}[health])
     return mc, (p0, v0, goal), kw
 
@@ -44,12 +45,12 @@ def _operands(h, N, B, stage, wind, smoother):
 _chain = {}
 
 
-def chain(h, N, B, stage, wind="rows", smoother="default", cycles=CYCLES):
+def chain(h, N, B, stage, wind="rows", smoother="default", cycles=CYCLES, substeps=SUBSTEPS, blocks=None):
     """ClosedLoopMonteCarlo.run for the configuration, as host arrays (computed once)."""
-    key = (id(h.ops), np.dtype(h.dt).name, N, B, stage, wind, smoother, cycles)
+    key = (id(h.ops), np.dtype(h.dt).name, N, B, stage, wind, smoother, cycles, substeps, blocks is not None)
     if key not in _chain:
-        mc, args, kw = _operands(h, N, B, stage, wind, smoother)
-        out = mc.run(*args, cycles, SUBSTEPS, SIM_DT, **kw)
+        mc, args, kw = _operands(h, N, B, stage, wind, smoother, blocks)
+        out = mc.run(*args, cycles, substeps, SIM_DT, **kw)
         _chain[key] = {k: np.array(h.to_host(v)) for k, v in out.items() if k in STATE_KEYS + ("smoother_state", "mixer_state")}
     return _chain[key]
 
@@ -60,12 +61,12 @@ def same_bits(a, b, what):
     assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), f"{what}: {int((a.view(np.uint8) != b.view(np.uint8)).sum())} bytes differ"
 
 
-def check_equals_chain(h, N, B, stage, wind="rows", smoother="default", last_plan=False):
+def check_equals_chain(h, N, B, stage, wind="rows", smoother="default", last_plan=False, cycles=CYCLES, substeps=SUBSTEPS, blocks=None):
     """run_fused_staged gives the bits of run: the drones' state, the clocks and every record; with `last_plan` also the last cycle's plan =
     a solve from the chain's state before its last act phase (the end of a chain of one cycle less)."""
-    ref = chain(h, N, B, stage, wind, smoother)
-    mc, args, kw = _operands(h, N, B, stage, wind, smoother)
-    got = mc.run_fused_staged(*args, CYCLES, SUBSTEPS, SIM_DT, want_last_plan=last_plan, **kw)
+    ref = chain(h, N, B, stage, wind, smoother, cycles, substeps, blocks)
+    mc, args, kw = _operands(h, N, B, stage, wind, smoother, blocks)
+    got = mc.run_fused_staged(*args, cycles, substeps, SIM_DT, want_last_plan=last_plan, **kw)
     with_smoother, with_mixer, _ = STAGES[stage]
     assert ("smoother_state" in got) == with_smoother == ("smoother_state" in ref)
     assert ("mixer_state" in got) == with_mixer == ("mixer_state" in ref)
@@ -77,7 +78,7 @@ def check_equals_chain(h, N, B, stage, wind="rows", smoother="default", last_pla
         return
     x = h.to_host(got["last_plan"]["x"])
     assert x.shape == (B, 9 * N)
-    before = chain(h, N, B, stage, wind, smoother, cycles=CYCLES - 1)
+    before = chain(h, N, B, stage, wind, smoother, cycles - 1, substeps, blocks)
     sol = h.ops.solve(mc.params, h.to_dev(before["pos"]), h.to_dev(before["vel"]), args[2], want_trajectory="accelerations")
     same_bits(x, h.to_host(sol["x"]), "last_plan x")
     same_bits(h.to_host(got["last_plan"]["accelerations"]), h.to_host(sol["accelerations"]), "last_plan accelerations")

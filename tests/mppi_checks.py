@@ -15,10 +15,11 @@ F32_TRACE_REL = 1e-3            # the minimum sample cost of iterations after th
 F64_REL = 1e-9
 
 
-def problem(N, nprob, seed, dt=0.1, K=0):
-    """A batch of small problems at dt = 0.1 s (the horizon covers metres), nominals inside the thrust box around hover."""
+def problem(N, nprob, seed, dt=0.1, K=0, params=None):
+    """A batch of small problems at dt = 0.1 s (the horizon covers metres), nominals inside the thrust box around hover.
+    params: overrides (e.g. a set of tests/param_sets.py) merged over the reference defaults at this horizon and dt."""
     rng = np.random.default_rng(seed)
-    prm = Params.reference_defaults(horizon=N, dt=dt)
+    prm = pc.make_params(N, params, dt=dt)
     cfg = pc.oracle_cfg(prm)
     p0 = rng.uniform(-1, 1, (nprob, 3)) + [0, 0, 2]
     v0 = rng.uniform(-1, 1, (nprob, 3))
@@ -79,9 +80,9 @@ def temperature_for(cfg, p0, v0, goal, U, S, sigma, seed, sph=None, w_obs=0.0):
     return float(np.median(c) - np.min(c))
 
 
-def check_against_oracle(h, N, S, nprob, iters, K=0, seed=5, sigma=1.0, w_obs=40.0):
+def check_against_oracle(h, N, S, nprob, iters, K=0, seed=5, sigma=1.0, w_obs=40.0, params=None):
     """U, cost, trace of the fused kernel against the float64 oracle (iters = 0 included: evaluate and copy)."""
-    prm, cfg, p0, v0, goal, U, sph = problem(N, nprob, seed, K=K)
+    prm, cfg, p0, v0, goal, U, sph = problem(N, nprob, seed, K=K, params=params)
     p0, v0, goal, U, sph = (_round(h, a) for a in (p0, v0, goal, U, sph))
     run = Run(h, prm, p0, v0, goal, U, sph, w_obs)
     lam = temperature_for(cfg, p0, v0, goal, U, S, sigma, seed, sph, w_obs)
@@ -108,10 +109,10 @@ def check_against_oracle(h, N, S, nprob, iters, K=0, seed=5, sigma=1.0, w_obs=40
             assert np.array_equal(Ud, U), "iters = 0 copies U_in"
 
 
-def check_limits(h, N, S, nprob, iters=3, K=0, seed=9, sigma=2.0):
+def check_limits(h, N, S, nprob, iters=3, K=0, seed=9, sigma=2.0, params=None):
     """lambda -> 0: the update is the best sample and the trace never increases; lambda -> inf: the update is the plain mean of the samples
     (se3mpc_population_sums_* with cost = NULL)."""
-    prm, cfg, p0, v0, goal, U, sph = problem(N, nprob, seed, K=K)
+    prm, cfg, p0, v0, goal, U, sph = problem(N, nprob, seed, K=K, params=params)
     run = Run(h, prm, p0, v0, goal, U, sph, 40.0)
     Ud, cd, trd, _ = run.host(run(S, iters, sigma, 1e-300, seed=seed, iter_base=5))
     assert np.all(np.diff(trd, axis=0) <= 0), "lambda -> 0: the trace is non-increasing"
@@ -137,10 +138,10 @@ def check_limits(h, N, S, nprob, iters=3, K=0, seed=9, sigma=2.0):
         assert np.max(np.abs(Uinf[p].reshape(-1) - mean)) <= tol, f"lambda -> inf: problem {p} moves to the plain mean"
 
 
-def check_composition(h, N, S, iters_seed=4, sigma=1.5):
+def check_composition(h, N, S, iters_seed=4, sigma=1.5, params=None):
     """Bit-level decomposition of one iteration (K = 0): mppi_samples -> rollout_cost_grad -> argmin -> population_sums(ref_key): the
     weighted mean equals one mppi iteration (f64: 1e-12, f32: 1e-6 relative to the box)."""
-    prm, cfg, p0, v0, goal, U, _ = problem(N, 1, iters_seed)
+    prm, cfg, p0, v0, goal, U, _ = problem(N, 1, iters_seed, params=params)
     run = Run(h, prm, p0, v0, goal, U)
     lam = temperature_for(cfg, p0, v0, goal, U, S, sigma, iters_seed)
     U1 = run.host(run(S, 1, sigma, lam, seed=iters_seed, iter_base=9))[0][0]

@@ -89,11 +89,11 @@ def same_bits(a, b, what):
         assert bits_equal(a[k], b[k]), f"{what}: {k}"
 
 
-def check_cycle_equivalence(h, N, B, K, S=64, cycles=3, substeps=3, sim_dt=0.01, shift=1, wind="per_drone", seed=5):
+def check_cycle_equivalence(h, N, B, K, S=64, cycles=3, substeps=3, sim_dt=0.01, shift=1, wind="per_drone", seed=5, **scene_kw):
     """One call with cycles = C == C chained calls with cycles = 1 and cycle_base = 0 .. C - 1, bit for bit, on the whole state, U, the
     clearance, the last cost and every trace row; drones [lo, hi) with index_base = lo == those rows of the full batch."""
     import torch
-    sc = Scene(h, N, B, K=K, S=S, wind=wind, seed=seed)
+    sc = Scene(h, N, B, K=K, S=S, wind=wind, seed=seed, **scene_kw)             # scene_kw: prm / cp / sp / ccfg / sim in place of the defaults
     one = sc.fresh()
     o1 = sc.call(one, cycles, substeps, sim_dt, shift, iter_base=7)
     many = sc.fresh()
@@ -114,12 +114,12 @@ def check_cycle_equivalence(h, N, B, K, S=64, cycles=3, substeps=3, sim_dt=0.01,
     return o1
 
 
-def check_planner_inside(h, N, B, K, S=64, substeps=4, sim_dt=0.01, seed=6):
+def check_planner_inside(h, N, B, K, S=64, substeps=4, sim_dt=0.01, seed=6, **scene_kw):
     """(a) cycles = 1, shift = 0, substeps = 0: U, cost and trace are those of se3mpc_mppi_* on the transposed operands, bit for bit.
     (b) plan_last against se3mpc_rollout_cost_grad_* (states) and se3mpc_extract_* (accelerations) at that U, to parity_checks' bounds.
     (c) plan_last fed to se3mpc_closed_loop_* from the same initial state reproduces the entry point's `substeps` steps."""
     import torch
-    sc = Scene(h, N, B, K=K, S=S, seed=seed)
+    sc = Scene(h, N, B, K=K, S=S, seed=seed, **scene_kw)
     rng = np.random.default_rng(seed)
     att0, om0 = rng.normal(0, 0.05, (B, 3)).astype(h.dt).astype(float), rng.normal(0, 0.1, (B, 3)).astype(h.dt).astype(float)
     st = sc.fresh(att=att0, omega=om0)
@@ -199,7 +199,7 @@ def device_state_to_oracle(sc, st):
                 clearance=f(st["clearance"]) if st["clearance"] is not None else np.full(B, np.inf))
 
 
-def check_against_oracle(h, N, B, K, S=64, cycles=3, substeps=3, sim_dt=0.01, shift=1, seed=8):
+def check_against_oracle(h, N, B, K, S=64, cycles=3, substeps=3, sim_dt=0.01, shift=1, seed=8, **scene_kw):
     """Cycle by cycle against the float64 NumPy chain started from the device's own state before the cycle (errors do not compound).
     U, cost, trace: the bounds of mppi_checks.  State after the cycle: f64 1e-8; f32 the closed-loop bounds of controller_checks
     (median over the drones 5e-3, every drone 5e-2).  The f32 bound needs no widening for the 2e-3 N the float32 nominal may differ by:
@@ -209,7 +209,7 @@ def check_against_oracle(h, N, B, K, S=64, cycles=3, substeps=3, sim_dt=0.01, sh
     (kp 18 on a simulator inertia of 0.1) turns into <= 0.09 rad/s^2: <= 1.4e-2 rad/s of body rate over tau, <= 1e-3 rad of attitude,
     <= 7e-4 m/s and <= 5e-5 m.  The largest of these, 1.4e-2, is inside the 5e-2 every drone is held to.
     Clearance: against the minimum over the positions the oracle's closed loop visited, to the positions' bound."""
-    sc = Scene(h, N, B, K=K, S=S, seed=seed)
+    sc = Scene(h, N, B, K=K, S=S, seed=seed, **scene_kw)
     st = sc.fresh()
     f32 = h.dt == np.float32
     for c in range(cycles):

@@ -48,13 +48,16 @@ def params(N):
     return Params.reference_defaults(horizon=N, dt=PLAN_DT)
 
 
-def _operands(h, shape, depth, substeps, wind="rows", cycles=CYCLES):
-    """-> (mc, positional arguments, keyword arguments) of run_mppi_edge / run_mppi_edge_fused for one configuration."""
+def _operands(h, shape, depth, substeps, wind="rows", cycles=CYCLES, blocks=None):
+    """-> (mc, positional arguments, keyword arguments) of run_mppi_edge / run_mppi_edge_fused for one configuration.
+    blocks: dict(prm, cp, sp, op) of parameter structs in place of the defaults (tests/param_sets.loop_blocks)."""
     N, B, K, S = shape
     p0, v0, goal, w, sph = (h.prob(a) for a in scene(B, K))
-    mc = ClosedLoopMonteCarlo(h.ops, params(N))
+    mc = ClosedLoopMonteCarlo(h.ops, params(N)) if blocks is None else ClosedLoopMonteCarlo(h.ops, blocks["prm"], blocks["cp"], blocks["sp"])
     kw = dict(seed=SEED, spheres=sph if K else None, obstacle_weight=W_OBS if K else 0.0, shift=None, latency_depth=depth,
               wind={"rows": w, None: None, "shared": w[0].contiguous()}[wind])
+    if blocks is not None:
+        kw["onboard"] = blocks["op"]
     return mc, (p0, v0, goal, cycles, substeps, SIM_DT, S, ITERS, SIGMA, LAM), kw
 
 
@@ -68,12 +71,12 @@ def _host(h, out, depth):
 _chain = {}
 
 
-def chain(h, shape, depth, substeps, wind="rows", cycles=CYCLES, log=False):
+def chain(h, shape, depth, substeps, wind="rows", cycles=CYCLES, log=False, blocks=None):
     """ClosedLoopMonteCarlo.run_mppi_edge for the configuration, as host arrays (computed once, never written).  With `log` also plan_last =
     the last cycle's plan and visited (cycles * substeps, B, 3) = the position after every simulator step."""
-    key = (id(h.ops), np.dtype(h.dt).name, shape, depth, substeps, wind, cycles, log)
+    key = (id(h.ops), np.dtype(h.dt).name, shape, depth, substeps, wind, cycles, log, blocks is not None)
     if key not in _chain:
-        mc, args, kw = _operands(h, shape, depth, substeps, wind, cycles)
+        mc, args, kw = _operands(h, shape, depth, substeps, wind, cycles, blocks)
         out = mc.run_mppi_edge(*args, log=log, **kw)
         assert out["clearance"] is None                                 # the chain measures no clearance: why the one launch exists
         res = _host(h, out, depth)
@@ -112,12 +115,12 @@ def check_not_vacuous(h, shape, substeps):
     assert moved > MOVES, moved
 
 
-def check_equals_chain(h, shape, depth, substeps, wind="rows", last_plan=False):
+def check_equals_chain(h, shape, depth, substeps, wind="rows", last_plan=False, cycles=CYCLES, blocks=None):
     """run_mppi_edge_fused gives the bytes of run_mppi_edge: the drones' state, the clocks, the onboard records, the counters, the nominal,
     the last cost and every trace row and -- with a buffer -- the latency records and the whole ring; with `last_plan` also the last cycle's
     plan, against the logged chain (which must itself fly the bytes of the unlogged one)."""
-    ref = chain(h, shape, depth, substeps, wind)
-    mc, args, kw = _operands(h, shape, depth, substeps, wind)
+    ref = chain(h, shape, depth, substeps, wind, cycles, blocks=blocks)
+    mc, args, kw = _operands(h, shape, depth, substeps, wind, cycles, blocks)
     got = mc.run_mppi_edge_fused(*args, want_last_plan=last_plan, **kw)
     assert got["logs"] == [] and got["latency"]["depth"] == depth and "controller_state" not in got
     what = f"{shape} depth={depth} substeps={substeps} wind={wind}"
@@ -130,7 +133,7 @@ def check_equals_chain(h, shape, depth, substeps, wind="rows", last_plan=False):
     if not last_plan:
         assert got["plan_last"] is None
         return
-    logged = chain(h, shape, depth, substeps, wind, log=True)
+    logged = chain(h, shape, depth, substeps, wind, cycles, log=True, blocks=blocks)
     same_run({k: logged[k] for k in ref}, ref, what + ": the logged chain against the unlogged")
     same_bits(h.to_host(got["plan_last"]), logged["plan_last"], what + ": plan_last")
 

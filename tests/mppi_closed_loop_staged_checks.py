@@ -44,16 +44,17 @@ def params(N):
     return Params.reference_defaults(horizon=N, dt=PLAN_DT)
 
 
-def _operands(h, shape, stage, wind="rows", smoother="default", shift=None, substeps=SUBSTEPS, cycles=CYCLES):
-    """-> (mc, positional arguments, keyword arguments) of run_mppi / run_mppi_fused_staged for one configuration."""
+def _operands(h, shape, stage, wind="rows", smoother="default", shift=None, substeps=SUBSTEPS, cycles=CYCLES, blocks=None):
+    """-> (mc, positional arguments, keyword arguments) of run_mppi / run_mppi_fused_staged for one configuration.
+    blocks: dict(prm, cp, sp, mixer) of parameter structs in place of the defaults (tests/param_sets.loop_blocks)."""
     N, B, K, S = shape
     p0, v0, goal, w, hl, sph = (h.prob(a) for a in scene(B, K))
     with_smoother, with_mixer, health = STAGES[stage] if stage is not None else (False, False, None)
-    mc = ClosedLoopMonteCarlo(h.ops, params(N))
+    mc = ClosedLoopMonteCarlo(h.ops, params(N)) if blocks is None else ClosedLoopMonteCarlo(h.ops, blocks["prm"], blocks["cp"], blocks["sp"])
     kw = dict(seed=SEED, spheres=sph if K else None, obstacle_weight=W_OBS if K else 0.0, shift=shift,
               wind={"rows": w, None: None, "shared": w[0].contiguous()}[wind],
               smoother=SmootherParams.reference_defaults(**SMOOTHERS[smoother]) if with_smoother else None,
-              mixer=h.ops.lib.mixer_default_params() if with_mixer else None,
+              mixer=(h.ops.lib.mixer_default_params() if blocks is None else blocks["mixer"]) if with_mixer else None,
               motor_health={"rows": hl, None: None, "shared": hl[0].contiguous()}[health])
     return mc, (p0, v0, goal, cycles, substeps, SIM_DT, S, ITERS, SIGMA, LAM), kw
 
@@ -66,22 +67,22 @@ def record_keys(stage):
 _chain = {}
 
 
-def chain(h, shape, stage, wind="rows", smoother="default", shift=None, substeps=SUBSTEPS):
+def chain(h, shape, stage, wind="rows", smoother="default", shift=None, substeps=SUBSTEPS, cycles=CYCLES, blocks=None):
     """ClosedLoopMonteCarlo.run_mppi for the configuration, as host arrays (computed once)."""
-    key = (id(h.ops), np.dtype(h.dt).name, shape, stage, wind, smoother, shift, substeps)
+    key = (id(h.ops), np.dtype(h.dt).name, shape, stage, wind, smoother, shift, substeps, cycles, blocks is not None)
     if key not in _chain:
-        mc, args, kw = _operands(h, shape, stage, wind, smoother, shift, substeps)
+        mc, args, kw = _operands(h, shape, stage, wind, smoother, shift, substeps, cycles, blocks)
         out = mc.run_mppi(*args, **kw)
         assert out["clearance"] is None or stage is None                           # the chain measures no clearance with a stage: why the feature exists
         _chain[key] = {k: np.array(h.to_host(out[k])) for k in STATE_KEYS + PLAN_KEYS + record_keys(stage)}
     return _chain[key]
 
 
-def check_equals_chain(h, shape, stage, wind="rows", smoother="default", shift=None, substeps=SUBSTEPS):
+def check_equals_chain(h, shape, stage, wind="rows", smoother="default", shift=None, substeps=SUBSTEPS, cycles=CYCLES, blocks=None):
     """run_mppi_fused_staged gives the bits of run_mppi: the drones' state, the clocks, every record, the nominal, the last cost and every
     trace row -- and a clearance where there are spheres."""
-    ref = chain(h, shape, stage, wind, smoother, shift, substeps)
-    mc, args, kw = _operands(h, shape, stage, wind, smoother, shift, substeps)
+    ref = chain(h, shape, stage, wind, smoother, shift, substeps, cycles, blocks)
+    mc, args, kw = _operands(h, shape, stage, wind, smoother, shift, substeps, cycles, blocks)
     got = mc.run_mppi_fused_staged(*args, **kw)
     for key in ("smoother_state", "mixer_state"):
         assert (key in got) == (key in record_keys(stage))

@@ -91,10 +91,10 @@ def check_zero_velocity_closed_loop(h, N, B, K, S=64, cycles=2, substeps=3, sim_
 
 
 # ---- 2. against the oracle -------------------------------------------------------------------------------------------------------------
-def crossing_problem(h, N, nprob, K, seed, t0=T0):
+def crossing_problem(h, N, nprob, K, seed, t0=T0, params=None):
     """mppi_checks.problem with velocities up to 3 m/s, sphere 0 (r = 0.5 m) aimed so that it covers problem 0's nominal at its last step
     and is far from it at the table's time."""
-    prm, cfg, p0, v0, goal, U, sph = mc.problem(N, nprob, seed, K=K)
+    prm, cfg, p0, v0, goal, U, sph = mc.problem(N, nprob, seed, K=K, params=params)
     p0, v0, goal, U = (_round(h, a) for a in (p0, v0, goal, U))
     vel = velocities(K, seed)
     if K and N > 1:
@@ -107,9 +107,9 @@ def crossing_problem(h, N, nprob, K, seed, t0=T0):
     return prm, cfg, p0, v0, goal, U, _round(h, sph), _round(h, vel)
 
 
-def check_against_oracle(h, N, S, nprob, iters, K, seed=5, sigma=1.0, w_obs=40.0, t0=T0):
+def check_against_oracle(h, N, S, nprob, iters, K, seed=5, sigma=1.0, w_obs=40.0, t0=T0, params=None):
     """U, cost, trace of se3mpc_mppi_moving_* against the float64 oracle, velocities up to 3 m/s (iters = 0 included)."""
-    prm, cfg, p0, v0, goal, U, sph, vel = crossing_problem(h, N, nprob, K, seed, t0)
+    prm, cfg, p0, v0, goal, U, sph, vel = crossing_problem(h, N, nprob, K, seed, t0, params=params)
     tR = mvo.step_times(N, cfg.dt, t0, h.dt)
     if K and N > 1:
         P, _ = orc.rollout(p0[0], v0[0], U[0], cfg)
@@ -168,11 +168,11 @@ def check_chunking_and_slices(h, N, S, nprob, K, iters=3, seed=13, sigma=1.0, t0
 
 
 # ---- 4. cycles in one call -------------------------------------------------------------------------------------------------------------
-def check_cycle_equivalence(h, N, B, K, S=64, cycles=3, substeps=3, sim_dt=0.01, shift=1, wind="per_drone", seed=5, t0=T0):
+def check_cycle_equivalence(h, N, B, K, S=64, cycles=3, substeps=3, sim_dt=0.01, shift=1, wind="per_drone", seed=5, t0=T0, **scene_kw):
     """cycles = C in one call == C chained calls with cycle_base = 0 .. C - 1, bit for bit, on what
     mppi_closed_loop_checks.check_cycle_equivalence compares: the tau bookkeeping of plan and clearance across launches."""
     import torch
-    sc = Scene(h, N, B, K=K, S=S, wind=wind, seed=seed, vel=velocities(K, seed), t0=t0)
+    sc = Scene(h, N, B, K=K, S=S, wind=wind, seed=seed, vel=velocities(K, seed), t0=t0, **scene_kw)
     one = sc.fresh()
     o1 = sc.call(one, cycles, substeps, sim_dt, shift, iter_base=7)
     many = sc.fresh()
@@ -196,11 +196,11 @@ def check_cycle_equivalence(h, N, B, K, S=64, cycles=3, substeps=3, sim_dt=0.01,
 
 
 # ---- 5. the planner inside -------------------------------------------------------------------------------------------------------------
-def check_planner_inside(h, N, B, K, S=64, run_substeps=4, sim_dt=0.01, seed=6, t0=T0):
+def check_planner_inside(h, N, B, K, S=64, run_substeps=4, sim_dt=0.01, seed=6, t0=T0, **scene_kw):
     """For C in {0, 2}: (a) cycles = 1, substeps = 0, shift = 0 at cycle_base = C == se3mpc_mppi_moving_* at the same sphere_t0 (with no
     simulator steps the cycle's base time is 0) and iteration numbers; (b) the same cycle of a run with `run_substeps` steps per cycle and
     sphere_t0 = 0 == se3mpc_mppi_moving_* called with (double)(C * run_substeps) * sim_dt -- U, cost and trace bit for bit."""
-    sc = Scene(h, N, B, K=K, S=S, seed=seed, vel=velocities(K, seed), t0=t0)
+    sc = Scene(h, N, B, K=K, S=S, seed=seed, vel=velocities(K, seed), t0=t0, **scene_kw)
     run = Run(h, sc.prm, sc.p0, sc.v0, sc.goal, sc.U0, sc.sph if K else None, sc.vel, sc.w_obs, t0)
     for C in (0, 2):
         for substeps, t_loop, t_plan in ((0, t0, t0), (run_substeps, 0.0, float(C * run_substeps) * sim_dt)):

@@ -23,10 +23,10 @@ def _same(a, b, what):
         assert np.array_equal(x, y), f"{what}: {name} differs"
 
 
-def check_against_oracle(h, N, S, splits, nprob, iters, K=0, seed=5, sigma=1.0, w_obs=40.0):
+def check_against_oracle(h, N, S, splits, nprob, iters, K=0, seed=5, sigma=1.0, w_obs=40.0, params=None):
     """U, cost, trace and keys of the split kernels against the float64 oracle, with the bounds of mppi_checks.check_against_oracle: they
     were set for float64 sums in a fixed order over the same samples, and another fixed order moves those sums in their last bits only."""
-    prm, cfg, p0, v0, goal, U, sph = mc.problem(N, nprob, seed, K=K)
+    prm, cfg, p0, v0, goal, U, sph = mc.problem(N, nprob, seed, K=K, params=params)
     p0, v0, goal, U, sph = (mc._round(h, a) for a in (p0, v0, goal, U, sph))
     run = Run(h, prm, p0, v0, goal, U, sph, w_obs)
     lam = mc.temperature_for(cfg, p0, v0, goal, U, S, sigma, seed, sph, w_obs)

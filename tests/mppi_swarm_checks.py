@@ -149,11 +149,11 @@ def chain(sc, st, cycles, substeps, sim_dt, shift, iter_base=0):
                 starts=starts)
 
 
-def check_chain(h, N, S, swarms, M, Kn, Ks, cycles=2, substeps=3, sim_dt=0.01, shift=1, seed=5, mates_matter=True):
+def check_chain(h, N, S, swarms, M, Kn, Ks, cycles=2, substeps=3, sim_dt=0.01, shift=1, seed=5, mates_matter=True, **scene_kw):
     """The main check: one swarm call == the per-drone chain of se3mpc_mppi_closed_loop_moving_* on swarm_oracle's tables, bit for bit on
     state, U, cost, trace and plan_last; the last cycle's neighbours and the separation (the cycle starts) equal the oracle's exactly."""
     p0 = np.concatenate([_spread(M, seed + s) for s in range(swarms)])
-    sc = Scene(h, N, swarms, M, Ks=Ks, Kn=Kn, S=S, seed=seed, p0=p0)
+    sc = Scene(h, N, swarms, M, Ks=Ks, Kn=Kn, S=S, seed=seed, p0=p0, **scene_kw)
     assert_no_ties(sc.p0, M)
     a, b = sc.fresh(), sc.fresh()
     ref = chain(sc, a, cycles, substeps, sim_dt, shift, iter_base=7)

@@ -63,3 +63,23 @@ def test_fused_monte_carlo_argument_checks(cpu_ops):
     assert lib.loop_status("monte_carlo", "f32", *args(B=-1)) == -3
     assert lib.loop_status("monte_carlo", "f32", *args(cycles=-1)) == -3
     assert lib.loop_status("monte_carlo", "f32", *args(over=0)) == -1
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_fused_monte_carlo_equals_the_two_launch_form_with_a_different_constant_in_every_block(cpu_ops, dtype):
+    """Every parameter block its own mass, gravity and max_thrust (tests/param_sets.LOOP_BLOCKS): at the defaults planner and simulator
+    agree (1.5 kg, 9.81 m/s^2), and a fused kernel that read one block's constant from another would still equal its chain."""
+    import param_sets as ps
+    from dart_planner_amd.control.closed_loop import ClosedLoopMonteCarlo
+    L = ps.LOOP_SHAPE
+    b = ps.loop_blocks(L["N"])
+    mc = ClosedLoopMonteCarlo(cpu_ops, b["prm"], b["cp"], b["sp"])
+    p0, v0, goal, wind = scene(L["B"], dtype)
+    a = mc.run(p0, v0, goal, L["cycles"], L["substeps"], 0.01, wind=wind)
+    f = mc.run_fused(p0, v0, goal, L["cycles"], L["substeps"], 0.01, wind=wind, want_last_plan=True)
+    for key in ("pos", "vel", "att", "omega", "time", "controller_state"):
+        assert torch.equal(a[key], f[key]), key
+    assert float((a["pos"] - p0).abs().max()) > 1e-3
+    # the blocks reach the flight: the same drones under the default blocks end elsewhere
+    d = ClosedLoopMonteCarlo(cpu_ops, b["prm"].copy(mass=1.5, gravity=9.81)).run(p0, v0, goal, L["cycles"], L["substeps"], 0.01, wind=wind)
+    assert not torch.equal(d["pos"], a["pos"])

@@ -181,3 +181,13 @@ def test_mppi_closed_loop_edge_checks_its_operands_before_any_call(emu_ops, monk
     assert calls == []
     ops.mppi_closed_loop_edge(mc.params, op, mc.simulator, st, buf, time, p0, v0, z, z.clone(), goal, U, cycles, substeps, sim_dt, S, iters, sigma, lam)
     assert calls == ["mppi_closed_loop_edge_f64"]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_fused_equals_chain_with_a_different_constant_in_every_block(emu_ops, dt):
+    """Every parameter block its own mass, gravity and max_thrust (tests/param_sets.LOOP_BLOCKS): at the defaults planner and simulator
+    agree (1.5 kg, 9.81 m/s^2), and a fused kernel that read one block's constant from another would still equal its chain."""
+    import param_sets as ps
+    L = ps.LOOP_SHAPE
+    ec.check_equals_chain(harness(emu_ops, dt), (L["N"], L["B"], L["K"], 64), 2, L["substeps"], last_plan=True, cycles=L["cycles"],
+                          blocks=ps.loop_blocks(L["N"], dt=ec.PLAN_DT))

@@ -145,3 +145,13 @@ def test_run_mppi_fused_still_has_no_stages(emu_ops):
         mc.run_mppi_fused(*args, smoother=capi.SmootherParams.reference_defaults())
     with pytest.raises(ValueError, match="mixer"):
         mc.run_mppi_fused(*args, mixer=emu_ops.lib.mixer_default_params())
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_fused_equals_chain_with_a_different_constant_in_every_block(emu_ops, dt):
+    """Every parameter block its own mass, gravity and max_thrust (tests/param_sets.LOOP_BLOCKS): at the defaults planner and simulator
+    agree (1.5 kg, 9.81 m/s^2), and a fused kernel that read one block's constant from another would still equal its chain."""
+    import param_sets as ps
+    L = ps.LOOP_SHAPE
+    sc.check_equals_chain(harness(emu_ops, dt), (L["N"], L["B"], L["K"], 64), "both_health", cycles=L["cycles"], substeps=L["substeps"],
+                          blocks=ps.loop_blocks(L["N"], dt=sc.PLAN_DT))

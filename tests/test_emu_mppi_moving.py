@@ -107,3 +107,15 @@ def _planner(ops):
 @pytest.mark.parametrize("dt", DTYPES)
 def test_front_end(emu_ops, dt):
     mv.check_front_end(harness(emu_ops, dt), _planner(emu_ops))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_a_different_constant_in_every_block(emu_ops, dt):
+    """Every parameter block its own mass, gravity and max_thrust (tests/param_sets.LOOP_BLOCKS): at the defaults planner and simulator
+    agree (1.5 kg, 9.81 m/s^2), and a fused kernel that read one block's constant from another would still equal its chain."""
+    import param_sets as ps
+    L = ps.LOOP_SHAPE
+    b = ps.loop_blocks(L["N"], dt=0.1)
+    kw = dict(prm=b["prm"], cp=b["cp"], sp=b["sp"], ccfg=b["ccfg"], sim=b["sim"])
+    mv.check_cycle_equivalence(harness(emu_ops, dt), L["N"], L["B"], L["K"], cycles=L["cycles"], substeps=L["substeps"], **kw)
+    mv.check_planner_inside(harness(emu_ops, dt), L["N"], L["B"], L["K"], run_substeps=L["substeps"], **kw)

@@ -18,6 +18,7 @@ pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/src/dart_plan
     ("make_golden_bifurcation.py", ["bifurcation_case.npz", "bifurcation_case.json"]),
     ("make_golden_controller.py", ["controller_cases.npz", "controller_cases.json"]),
     ("make_golden.py", ["solve_cases.npz", "solve_cases.json", "path_functions.npz", "path_functions.json", "mapper_spheres.npz", "mapper_spheres.json"]),
+    ("make_golden_params.py", ["param_cases.npz", "param_cases.json"]),
 ])
 def test_generator_reproduces_committed_fixtures(tmp_path, script, files):
     env = dict(os.environ, SE3MPC_GOLDEN_OUT=str(tmp_path), PYTHONDONTWRITEBYTECODE="1")

@@ -486,3 +486,28 @@ def test_plan_operand_rules_of_every_entry_point(gpu_ops, dt):
 @pytest.mark.parametrize("dt", [np.float64, np.float32])
 def test_front_ends_refuse_wrong_operands_before_any_launch(gpu_ops, dt, monkeypatch):
     cc.check_operand_rules(harness(gpu_ops, dt), monkeypatch)
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_monte_carlo_in_one_launch_equals_the_two_launch_form_with_a_different_constant_in_every_block(gpu_ops, prec):
+    """Every parameter block its own mass, gravity and max_thrust (tests/param_sets.LOOP_BLOCKS): at the defaults planner and simulator
+    agree (1.5 kg, 9.81 m/s^2), and a fused kernel that read one block's constant from another would still equal its chain."""
+    import torch
+    import param_sets as ps
+    from dart_planner_amd.control.closed_loop import ClosedLoopMonteCarlo
+    dtype = torch.float32 if prec == "f32" else torch.float64
+    dev = gpu_ops.be.device
+    L = ps.LOOP_SHAPE
+    b = ps.loop_blocks(L["N"])
+    mc = ClosedLoopMonteCarlo(gpu_ops, b["prm"], b["cp"], b["sp"])
+    g = torch.Generator(device=dev); g.manual_seed(5)
+    B = L["B"]
+    p0 = torch.tensor([0.0, 0.0, 2.0], dtype=dtype, device=dev).repeat(B, 1) + 0.2 * torch.randn(B, 3, dtype=dtype, device=dev, generator=g)
+    v0 = 0.3 * torch.randn(B, 3, dtype=dtype, device=dev, generator=g)
+    goal = torch.tensor([8.0, 0.0, 5.0], dtype=dtype, device=dev).repeat(B, 1).contiguous()
+    wind = torch.randn(B, 3, dtype=dtype, device=dev, generator=g).contiguous()
+    a = mc.run(p0, v0, goal, L["cycles"], L["substeps"], 0.01, wind=wind)
+    f = mc.run_fused(p0, v0, goal, L["cycles"], L["substeps"], 0.01, wind=wind, want_last_plan=True)
+    for key in ("pos", "vel", "att", "omega", "time", "controller_state"):
+        assert torch.equal(a[key], f[key]), key
+    assert torch.isfinite(f["pos"]).all() and float((f["pos"] - p0).abs().max()) > 1e-3

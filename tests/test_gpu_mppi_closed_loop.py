@@ -73,3 +73,16 @@ def test_invalid_arguments(gpu_ops, dt):
 @pytest.mark.parametrize("dt", DTYPES)
 def test_front_end(gpu_ops, dt):
     lc.check_front_end(harness(gpu_ops, dt))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_a_different_constant_in_every_block(gpu_ops, dt):
+    """Every parameter block its own mass, gravity and max_thrust (tests/param_sets.LOOP_BLOCKS): at the defaults planner and simulator
+    agree (1.5 kg, 9.81 m/s^2), and a fused kernel that read one block's constant from another would still equal its chain."""
+    import param_sets as ps
+    L = ps.LOOP_SHAPE
+    b = ps.loop_blocks(L["N"], dt=0.1)
+    kw = dict(prm=b["prm"], cp=b["cp"], sp=b["sp"], ccfg=b["ccfg"], sim=b["sim"])
+    lc.check_cycle_equivalence(harness(gpu_ops, dt), L["N"], L["B"], L["K"], cycles=L["cycles"], substeps=L["substeps"], **kw)
+    lc.check_planner_inside(harness(gpu_ops, dt), L["N"], L["B"], L["K"], substeps=L["substeps"], **kw)
+    lc.check_against_oracle(harness(gpu_ops, dt), L["N"], L["B"], L["K"], cycles=L["cycles"], substeps=L["substeps"], **kw)

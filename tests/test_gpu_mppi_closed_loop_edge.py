@@ -85,3 +85,13 @@ def test_without_steps_it_is_the_planner_and_touches_no_record(gpu_ops, dt, shap
 @pytest.mark.parametrize("dt", DTYPES)
 def test_argument_rules(gpu_ops, dt):
     ec.check_argument_rules(harness(gpu_ops, dt))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_fused_equals_chain_with_a_different_constant_in_every_block(gpu_ops, dt):
+    """Every parameter block its own mass, gravity and max_thrust (tests/param_sets.LOOP_BLOCKS): at the defaults planner and simulator
+    agree (1.5 kg, 9.81 m/s^2), and a fused kernel that read one block's constant from another would still equal its chain."""
+    import param_sets as ps
+    L = ps.LOOP_SHAPE
+    ec.check_equals_chain(harness(gpu_ops, dt), (L["N"], L["B"], L["K"], 64), 2, L["substeps"], last_plan=True, cycles=L["cycles"],
+                          blocks=ps.loop_blocks(L["N"], dt=ec.PLAN_DT))

@@ -85,3 +85,14 @@ def test_invalid_arguments(gpu_ops, dt):
 @pytest.mark.parametrize("dt", DTYPES)
 def test_front_end(gpu_ops, dt):
     sw.check_front_end(harness(gpu_ops, dt))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_equals_the_per_drone_chain_with_a_different_constant_in_every_block(gpu_ops, dt):
+    """Every parameter block its own mass, gravity and max_thrust (tests/param_sets.LOOP_BLOCKS): at the defaults planner and simulator
+    agree (1.5 kg, 9.81 m/s^2), and a fused kernel that read one block's constant from another would still equal its chain."""
+    import param_sets as ps
+    L = ps.LOOP_SHAPE
+    b = ps.loop_blocks(L["N"], dt=0.1)
+    sw.check_chain(harness(gpu_ops, dt), L["N"], 64, 1, L["B"], 2, L["K"], cycles=L["cycles"], substeps=L["substeps"], mates_matter=False,
+                   prm=b["prm"], cp=b["cp"], sp=b["sp"], ccfg=b["ccfg"], sim=b["sim"])

@@ -57,3 +57,31 @@ def test_port_matches_scipy_on_generic_box_problems(seed):
         assert (r.nit, r.nfev, r.status) == (res.nit, res.nfev, res.status), (seed, m, r.task, res.message)
         assert np.allclose(r.x, res.x, rtol=0, atol=1e-9)
         assert len(tr) == len(r.trace) and all(np.allclose(a, b_, atol=1e-6) for a, b_ in zip(r.trace, tr))  # rounding-order noise is amplified mid-run on Rosenbrock
+
+
+@pytest.mark.parametrize("N", [6, 20, 30])
+@pytest.mark.parametrize("limits", [dict(m=1), dict(m=3), dict(m=5), dict(maxls=2), dict(maxfun=12), dict(m=3, maxls=2, maxfun=12)],
+                         ids=lambda d: "-".join(f"{k}{v}" for k, v in d.items()))
+def test_port_follows_scipy_off_the_default_limits(N, limits):
+    """maxcor, maxls and maxfun at valid non-default values on the tight-tolerance problems of parity_checks.check_solver_limits (the
+    reference's objective and its inconsistent gradient; pgtol 1e-9, ftol 1e-8, 40 iterations: the memory wraps, line searches fail, the
+    evaluation count passes maxfun -- where SciPy reports status 1 even when the last line search ended abnormally)."""
+    import parity_checks as pc
+    from dart_planner_amd.capi import Params
+    cfg = pc.oracle_cfg(Params.reference_defaults(horizon=N, **pc.TIGHT))
+    p0, v0, goal = pc.limit_problems(np.random.default_rng(21), 16, N, "short")
+    b = orc.bounds(cfg)
+    seen = set()
+    for i in range(16):
+        x0 = orc.straight_line_init(p0[i], v0[i], goal[i], cfg)
+        fg = lambda x: (orc.objective_ordered(x, goal[i], cfg), orc.gradient(x, goal[i], cfg))
+        kw = dict(m=10, maxls=20, maxfun=15000); kw.update(limits)
+        r = lb.minimize(fg, x0, b[:, 0], b[:, 1], ftol=pc.TIGHT["ftol"], pgtol=pc.TIGHT["pgtol"], maxiter=pc.TIGHT["max_iterations"], **kw)
+        res = minimize(lambda x: fg(x)[0], x0, jac=lambda x: fg(x)[1], method="L-BFGS-B", bounds=list(zip(b[:, 0], b[:, 1])),
+                       options=dict(maxiter=pc.TIGHT["max_iterations"], gtol=pc.TIGHT["pgtol"], ftol=pc.TIGHT["ftol"], maxcor=kw["m"],
+                                    maxls=kw["maxls"], maxfun=kw["maxfun"]))
+        assert (r.nit, r.nfev, r.status) == (res.nit, res.nfev, res.status), (i, limits, r.task, res.message)
+        assert np.allclose(r.x, res.x, rtol=0, atol=1e-9)
+        seen.add((res.status, "ABNORMAL" in str(res.message).upper()))
+    if limits.get("maxfun") == 12 and len(limits) == 1:
+        assert (1, True) in seen and (1, False) in seen, seen       # SciPy ended past maxfun in both of its ways, status 1 each time

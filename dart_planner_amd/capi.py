@@ -269,12 +269,45 @@ class OnboardParams(C.Structure):
 
 assert C.sizeof(OnboardParams) == 216     # static_assert of csrc/edge_device.hpp
 
+
+class MissionParams(C.Structure):
+    """struct se3mpc_mission_params == the literals of GlobalMissionPlanner.get_current_goal and what it reads of GlobalMissionConfig
+    (src/dart_planner/planning/global_mission_planner.py:46-60, :254-261, :322, :347, :358, :380, :411-413, :454)."""
+    _fields_ = [(n, C.c_double) for n in ("safe_altitude", "takeoff_band", "waypoint_reach", "safety_margin", "landing_pad_lift", "landing_step",
+                                         "landing_floor", "emergency_step", "emergency_floor", "emergency_altitude", "global_replan_period",
+                                         "exploration_base", "exploration_radius", "stamp_radius", "stamp_factor")] + [
+        ("use_neural_scene", C.c_int32), ("reserved", C.c_int32)]
+
+    @classmethod
+    def reference_defaults(cls, **overrides) -> "MissionParams":
+        """The reference's literals, computed here the way se3mpc_mission_default_params() does (the test-suite checks the two agree)."""
+        p = cls(safe_altitude=5.0, takeoff_band=0.5, waypoint_reach=2.0, safety_margin=2.0, landing_pad_lift=3.0, landing_step=1.0, landing_floor=0.5,
+                emergency_step=2.0, emergency_floor=0.0, emergency_altitude=0.5, global_replan_period=1.0 / 1.0, exploration_base=10.0,
+                exploration_radius=50.0, stamp_radius=3.0, stamp_factor=0.2, use_neural_scene=1, reserved=0)
+        return p.copy(**overrides) if overrides else p
+
+    def copy(self, **overrides) -> "MissionParams":
+        q = type(self)()
+        C.memmove(C.byref(q), C.byref(self), C.sizeof(type(self)))
+        for k, v in overrides.items():
+            if k not in dict(self._fields_):
+                raise AttributeError(f"se3mpc_mission_params has no field {k!r}")
+            setattr(q, k, int(bool(v)) if k == "use_neural_scene" else float(v))
+        return q
+
+
+assert C.sizeof(MissionParams) == 128     # static_assert of csrc/mission_device.hpp
+
 CONTROLLER_STATE_WORDS = 12
 SMOOTHER_STATE_WORDS = 25
 MIXER_STATE_WORDS = 5
 ONBOARD_STATE_WORDS = 14
 LATENCY_STATE_WORDS = 4
 LATENCY_MAX_DEPTH = 1000
+MISSION_STATE_WORDS = 4
+# MissionPhase in the reference's order, and the semantic labels the goal rule tells apart (include/se3mpc.h)
+MISSION_PHASES = ("takeoff", "exploration", "mapping", "navigation", "landing", "emergency")
+MISSION_LABELS = {"obstacle": 1, "landing_pad": 2, "doorway": 3}
 # flag bits of se3mpc_mixer_mix_* (include/se3mpc.h)
 MIXER_NEGATIVE_THRUST, MIXER_NON_FINITE, MIXER_OVERRUN, MIXER_SATURATION_EVENT, MIXER_ALL_IDLE, MIXER_WATCHDOG = 1, 2, 4, 8, 16, 32
 
@@ -345,6 +378,7 @@ _SP = C.POINTER(SimulatorParams)
 _MP = C.POINTER(SmootherParams)
 _XP = C.POINTER(MixerParams)
 _OP = C.POINTER(OnboardParams)
+_GP = C.POINTER(MissionParams)
 _LL = C.c_longlong
 _PLAN = [_I, _P, _LL, _P, _LL, _P, _LL, _P, _LL]            # N, timestamps, ts_stride, P, strideP, V, strideV, A, strideA
 # consumer side of the contract: se3mpc_<base>_<suffix>(...)
@@ -373,6 +407,9 @@ _LOOP_TYPED_API = {
     "monte_carlo": [_PP, _CP, _SP, _I, _I, _I, _D, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "monte_carlo_staged": [_PP, _CP, _SP, _MP, _XP, _I, _I, _I, _D, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _P, _P, _P, _P],
     "monte_carlo_edge": [_PP, _OP, _SP, _I, _I, _I, _D, _I, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mission_goal": [_GP, _I, _P, _P, _P, _P, _LL, _P, _LL, _I, _D, _P, _P, _P, _P, _P, _P],
+    "monte_carlo_mission": [_PP, _CP, _SP, _GP, _I, _I, _I, _D, _I, _D, _P, _LL, _P, _LL, _I, _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                            _P, _P, _P, _P, _P],
     "mppi_closed_loop": [_PP, _CP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _D, _P, _LL,
                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mppi_closed_loop_moving": [_PP, _CP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, _D, _I,
@@ -396,6 +433,9 @@ _PLAIN_API = {
     "se3mpc_onboard_default_params": (C.c_int, [_OP]),
     "se3mpc_onboard_reset": (C.c_int, [_I, _P, _P]),
     "se3mpc_latency_reset": (C.c_int, [_I, _I, _P, _P]),
+    "se3mpc_mission_default_params": (C.c_int, [_GP]),
+    "se3mpc_check_mission_params": (C.c_int, [_GP]),
+    "se3mpc_mission_reset": (C.c_int, [_I, _P, _P]),
     "se3mpc_abi_version": (C.c_int, []),
     "se3mpc_last_error": (C.c_char_p, []),
     "se3mpc_device_count": (C.c_int, []),
@@ -577,6 +617,17 @@ class Library:
     def latency_reset(self, B: int, depth: int, state: int, stream: int) -> None:
         self._check("se3mpc_latency_reset", self._dll.se3mpc_latency_reset(B, depth, state, stream))
 
+    def mission_default_params(self) -> MissionParams:
+        p = MissionParams()
+        self._check("se3mpc_mission_default_params", self._dll.se3mpc_mission_default_params(C.byref(p)))
+        return p
+
+    def check_mission_params(self, mp: Optional[MissionParams]) -> int:
+        return self._dll.se3mpc_check_mission_params(C.byref(mp) if mp is not None else None)
+
+    def mission_reset(self, B: int, state: int, stream: int) -> None:
+        self._check("se3mpc_mission_reset", self._dll.se3mpc_mission_reset(B, state, stream))
+
     def loop_call(self, base: str, suffix: str, *args) -> None:
         """se3mpc_control_<suffix> / se3mpc_closed_loop_<suffix>; struct arguments are passed by reference here."""
         a = [C.byref(x) if isinstance(x, _STRUCTS) else x for x in args]
@@ -626,7 +677,7 @@ class Library:
             raise Se3mpcError(name, rc, self.last_error() if rc == -6 else "")
 
 
-_STRUCTS = (ControllerParams, SimulatorParams, SmootherParams, MixerParams, OnboardParams, Params)
+_STRUCTS = (ControllerParams, SimulatorParams, SmootherParams, MixerParams, OnboardParams, MissionParams, Params)
 _default: Optional[Library] = None
 
 

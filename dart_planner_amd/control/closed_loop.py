@@ -18,6 +18,9 @@ same planner: a latency buffer between the drone's state and its controller, and
 (``se3mpc_edge_loop_*``); ``run_edge_fused`` flies it inside one launch (``se3mpc_monte_carlo_edge_*``).
 ``run_mppi_edge`` / ``run_mppi_edge_fused`` fly that edge loop under the MPPI planner, as a chain and in one launch
 (``se3mpc_mppi_closed_loop_edge_*``): the one form where the delay and the obstacle clearance meet.
+``run_mission`` / ``run_mission_fused`` fly waypoint missions: the goal of every cycle comes from the reference's
+GlobalMissionPlanner.get_current_goal on the drone's own position (``se3mpc_mission_goal_*``, ``se3mpc_monte_carlo_mission_*``)
+where every other method holds one goal for the whole run.
 """
 import math
 from typing import Optional
@@ -208,6 +211,130 @@ class ClosedLoopMonteCarlo:
         if int(ops.be.to_host(out["overflowed"])[0]) != 0:
             return self.run(p0, v0, goal, cycles, substeps, sim_dt, wind=wind)
         return self._result(st, sm, fl, logs=[], last_plan=out if want_last_plan else None)
+
+    _MISSION_UNBUILT = ("smoother", "mixer", "motor_health", "latency_depth", "onboard", "swarm_size", "neighbours", "mate_radius", "sphere_velocities")
+
+    @classmethod
+    def _no_mission_form(cls, options: dict, what: str) -> None:
+        bad = sorted(k for k in options if k in cls._MISSION_UNBUILT and options[k] is not None)
+        if bad:
+            raise ValueError(f"{what}: missions are not built under the smoother, mixer, edge, swarm or moving-sphere forms ({', '.join(bad)}; "
+                             "DESIGN.md 5.10): fly them with planner='solve' or planner='mppi' alone")
+
+    @staticmethod
+    def _mission_field(field):
+        """field: None, the mirror's UncertaintyField or a capi.UFieldDesc -> (descriptor or None, the resolution the stamps are made for)."""
+        if field is None:
+            return None, 1.0
+        desc = getattr(field, "_desc", field)
+        return desc, float(desc.resolution)
+
+    def _mission_result(self, st, fl, ms, goal, **more):
+        """The result of a mission run: :meth:`run`'s keys, the mission records, the last goal, and phase / waypoint_index as int32 copies of
+        the records' first two words."""
+        import torch
+        return self._result(st, None, fl, mission_state=ms, goal=goal, phase=ms[:, 0].to(torch.int32), waypoint_index=ms[:, 1].to(torch.int32), **more)
+
+    def run_mission(self, p0, v0, waypoints, labels, cycles: int, substeps: int, sim_dt: float, mission=None, planner: str = "solve",
+                    epoch: float = 1000.0, field=None, wind=None, log: bool = False, n_samples: int = 0, iters: int = 0, sigma: float = 0.0,
+                    temperature: float = 1.0, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, shift: Optional[int] = None, nominal=None,
+                    **unbuilt):
+        """The receding-horizon Monte-Carlo flying waypoint missions: before every plan the goal comes from the reference's
+        GlobalMissionPlanner.get_current_goal on the drone's own position (``se3mpc_mission_goal_*``), where every other form holds one goal
+        for the whole run.  waypoints: float64 (W, 3) shared by all drones or (B, W, 3); labels: int32 (W,) or (B, W), 0 = any label, 1 =
+        "obstacle", 2 = "landing_pad", 3 = "doorway"; mission: capi.MissionParams (None: the reference's literals).  Per cycle, in order:
+        one mission-goal launch with now = the drones' clocks + `epoch` (the default exceeds the replan period, so the first call makes a
+        global plan, as against a real wall clock); with `field` (the mirror's UncertaintyField, or a capi.UFieldDesc) one
+        ``se3mpc_ufield_stamp`` launch over the B rows the global plans stamped -- the drones share one scene, row order = B sequential calls;
+        then the cycle of :meth:`run` (planner="solve") or of :meth:`run_mppi` (planner="mppi", with its arguments; the clearance continues in
+        place from call to call).  No host round trip: the goal is a device tensor from launch to launch.
+        -> what :meth:`run` / :meth:`run_mppi` returns, plus mission_state (B, 4), goal (B, 3) = the last cycle's, phase and waypoint_index
+        int32 (B,); with `log` also goals (cycles, B, 3) and phases int32 (cycles, B), each cycle's after its mission call."""
+        import torch
+        self._no_mission_form(unbuilt, "run_mission")
+        if set(unbuilt) - set(self._MISSION_UNBUILT):
+            raise TypeError(f"run_mission: unexpected arguments {sorted(set(unbuilt) - set(self._MISSION_UNBUILT))}")
+        if planner not in ("solve", "mppi"):
+            raise ValueError(f"run_mission: planner {planner!r} (\"solve\" or \"mppi\")")
+        ops, prm = self.ops, self.params
+        B, N = p0.shape[0], prm.horizon
+        mp = mission if mission is not None else ops.lib.mission_default_params()
+        desc, resolution = self._mission_field(field)
+        st, _, fl = self._start(p0, v0)
+        ms = ops.mission_state(B)
+        goal, stamps = torch.zeros_like(p0), ops.mission_stamps(B)
+        goals, phases, logs, traces, out, clr, sols = [], [], [], [], None, None, [None]
+        if planner == "solve":
+            act = self._actor(None, st, None, fl, (9 * N, 9 * N, 3 * N), substeps, sim_dt, wind)
+            k = torch.arange(N, dtype=torch.float64, device=ops.be.device)
+        else:
+            U = self._mppi_start(p0, nominal)
+            sh = self.resolve_shift(substeps, sim_dt, shift)
+        for c in range(cycles):
+            ops.mission_goal(mp, ms, fl[0] + epoch, fl[1], waypoints, labels, resolution, goal=goal, stamps=stamps)
+            if desc is not None:
+                ops.ufield_stamp(desc, stamps["centres"], stamps["radius"], stamps["radius_voxels"], stamps["factor"])
+            if log:
+                goals.append(goal.clone())
+                phases.append(ms[:, 0].to(torch.int32))
+            if planner == "solve":
+                sol = sols[0] = ops.solve(prm, fl[1], fl[2], goal, want_trajectory=True if log else "accelerations", out=None if log else sols[0])
+                X = sol["x"]
+                flown = act(((c * substeps * sim_dt) + k * prm.dt, X, X[:, 3 * N:], sol["accelerations"]), log)
+                if log:
+                    logs.append((sol, flown))
+            else:
+                out = ops.mppi_closed_loop(prm, self.controller, self.simulator, st, *fl, goal, U, 1, substeps, sim_dt, n_samples, iters, sigma, temperature,
+                                           seed=seed, cycle_base=c, shift=sh, spheres=spheres, obstacle_weight=obstacle_weight, wind=wind, want_plan=log,
+                                           clearance=clr)
+                clr = out["clearance"]
+                traces.append(out["trace"])
+                if log:
+                    logs.append(dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"]))
+        more = dict(logs=logs)
+        if planner == "mppi":
+            trace = torch.cat(traces, dim=1) if traces else torch.zeros(B, 0, max(int(iters), 0), dtype=p0.dtype, device=ops.be.device)
+            more.update(U=U, cost=None if out is None else out["cost"], trace=trace, clearance=clr)
+        if log:
+            more.update(goals=torch.stack(goals) if goals else torch.zeros(0, B, 3, dtype=p0.dtype, device=ops.be.device),
+                        phases=torch.stack(phases) if phases else torch.zeros(0, B, dtype=torch.int32, device=ops.be.device))
+        return self._mission_result(st, fl, ms, goal, **more)
+
+    def run_mission_fused(self, p0, v0, waypoints, labels, cycles: int, substeps: int, sim_dt: float, mission=None, epoch: float = 1000.0,
+                          field=None, wind=None, want_last_plan: bool = False, first_cycle: int = 0, resume=None, **unbuilt):
+        """:meth:`run_mission` with planner="solve" in ONE launch (``se3mpc_monte_carlo_mission_*``): every cycle's mission call,
+        solve and control / simulator steps inside one kernel, where :meth:`run_mission` makes three launches per cycle.  Same code, same bits
+        and the same result keys as :meth:`run_mission` (no logs), plus last_plan as :meth:`run_fused`.  The stamps cannot be applied inside
+        the launch -- they are ordered writes to a grid all drones share, and the phase machine never reads it: with `field` the kernel logs
+        them and ONE ``se3mpc_ufield_stamp`` call of cycles x B rows applies them afterwards, in the chain's order (cycle-major, drone-minor),
+        so the grids come out with the chain's bytes.  All cross-cycle state is in the returned operands: ``resume=`` a result of this method
+        with ``first_cycle=`` the cycles it flew continues that run (p0, v0 are then not read).  If a solve needed more L-BFGS memory than
+        the launch's LDS image holds (never with the reference's options) the run is repeated by :meth:`run_mission`.
+
+        Measured on an MI355X: DESIGN.md 5.10 (``tools/gpu_probe_mission.py``, ``profiles/mission.json``)."""
+        self._no_mission_form(unbuilt, "run_mission_fused")
+        if set(unbuilt) - set(self._MISSION_UNBUILT):
+            raise TypeError(f"run_mission_fused: unexpected arguments {sorted(set(unbuilt) - set(self._MISSION_UNBUILT))}")
+        ops = self.ops
+        mp = mission if mission is not None else ops.lib.mission_default_params()
+        desc, resolution = self._mission_field(field)
+        if resume is None:
+            st, _, fl = self._start(p0, v0)
+            ms, goal = ops.mission_state(p0.shape[0]), None
+        else:
+            st, ms, goal = resume["controller_state"], resume["mission_state"], resume["goal"]
+            fl = tuple(resume[k] for k in ("time", "pos", "vel", "att", "omega"))
+        out = ops.monte_carlo_mission(self.params, self.controller, self.simulator, mp, st, ms, *fl, waypoints, labels, cycles, substeps, sim_dt,
+                                      epoch=epoch, resolution=resolution, wind=wind, first_cycle=first_cycle, goal=goal, want_stamps=desc is not None,
+                                      want_last_plan=want_last_plan)
+        if int(ops.be.to_host(out["overflowed"])[0]) != 0:
+            if resume is not None:
+                raise RuntimeError("run_mission_fused: a solve overflowed the launch's LDS image in a resumed run; fly the whole run with run_mission")
+            return self.run_mission(p0, v0, waypoints, labels, cycles, substeps, sim_dt, mission=mission, epoch=epoch, field=field, wind=wind)
+        if desc is not None and cycles > 0:
+            s = out["stamps"]
+            ops.ufield_stamp(desc, s["centres"], s["radius"], s["radius_voxels"], s["factor"])
+        return self._mission_result(st, fl, ms, out["goal"], logs=[], last_plan=out if want_last_plan else None)
 
     def run_fused_staged(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, wind=None, want_last_plan: bool = False,
                          smoother: Optional[SmootherParams] = None, mixer: Optional[MixerParams] = None, motor_health=None):

@@ -17,9 +17,9 @@ import ctypes as _C
 
 import numpy as np
 
-from .capi import (CONTROLLER_STATE_WORDS, LATENCY_MAX_DEPTH, LATENCY_STATE_WORDS, MIXER_STATE_WORDS, ONBOARD_STATE_WORDS, SMOOTHER_STATE_WORDS,
-                   SE3MPC_MAX_SPHERES, ControllerParams, Library, MixerParams, OnboardParams, Params, SimulatorParams, SmootherParams, SolveInfo,
-                   UFieldDesc, get_library)
+from .capi import (CONTROLLER_STATE_WORDS, LATENCY_MAX_DEPTH, LATENCY_STATE_WORDS, MISSION_STATE_WORDS, MIXER_STATE_WORDS, ONBOARD_STATE_WORDS,
+                   SMOOTHER_STATE_WORDS, SE3MPC_MAX_SPHERES, ControllerParams, Library, MissionParams, MixerParams, OnboardParams, Params,
+                   SimulatorParams, SmootherParams, SolveInfo, UFieldDesc, get_library)
 
 INFO_DTYPE = np.dtype([("fun", "<f8"), ("nit", "<i4"), ("nfev", "<i4"), ("status", "<i4"), ("task", "<i4")])
 assert INFO_DTYPE.itemsize == 24
@@ -1491,6 +1491,95 @@ class Ops:
         self.lib.ufield_targets(self.be.ptr(regions), self.be.ptr(counts), int(num_targets), position, self.be.ptr(targets), self.be.ptr(n_out),
                                 self.be.stream())
         return targets, n_out
+
+    # ------------------------------------------------------------------ mission layer: the goal source
+    def mission_state(self, B: int):
+        """Fresh mission records for B drones (GlobalMissionPlanner.__init__: TAKEOFF, waypoint 0, no global plan yet): float64 (B, 4)."""
+        st = self.be.empty((B, MISSION_STATE_WORDS), "f64")
+        self.lib.mission_reset(B, self.be.ptr(st), self.be.stream())
+        return st
+
+    def _mission_record(self, state, B):
+        self.be.check(state, "mission state")
+        if tuple(state.shape) != (B, MISSION_STATE_WORDS) or self.be.suffix(state) != "f64":
+            raise ValueError(f"mission state: float64 ({B}, {MISSION_STATE_WORDS})")
+
+    def _waypoints(self, waypoints, labels, B) -> list:
+        """A waypoint table: positions float64 (W, 3) shared by all drones or (B, W, 3) per drone, labels int32 (W,) or (B, W) -> the five
+        table arguments (waypoints, wp_stride, labels, label_stride, W)."""
+        self.be.check(waypoints, "waypoints")
+        self.be.check(labels, "labels")
+        if self.be.suffix(waypoints) != "f64" or waypoints.ndim not in (2, 3) or waypoints.shape[-1] != 3 or (waypoints.ndim == 3 and waypoints.shape[0] != B):
+            raise ValueError(f"waypoints: float64 (W, 3) or ({B}, W, 3), got {tuple(waypoints.shape)}")
+        W = waypoints.shape[-2]
+        if not str(labels.dtype).endswith("int32") or tuple(labels.shape) not in ((W,), (B, W)):
+            raise ValueError(f"labels: int32 ({W},) or ({B}, {W}), got {labels.dtype} {tuple(labels.shape)}")
+        return [self.be.ptr(waypoints if W else None), 3 * W if waypoints.ndim == 3 else 0, self.be.ptr(labels if W else None), W if labels.ndim == 2 else 0, W]
+
+    def mission_stamps(self, rows: int):
+        """An empty stamp table of `rows` rows in the operand form of :meth:`ufield_stamp`: dict(centres (rows, 3), radius (rows,),
+        radius_voxels int32 (rows,), factor (rows,))."""
+        return dict(centres=self.be.empty((rows, 3), "f64"), radius=self.be.empty((rows,), "f64"), radius_voxels=self.be.empty((rows,), "i32"),
+                    factor=self.be.empty((rows,), "f64"))
+
+    def _stamps(self, stamps, rows):
+        self._f64(stamps["centres"], (rows, 3), "stamp centres")
+        self._f64(stamps["radius"], (rows,), "stamp radius")
+        self._f64(stamps["factor"], (rows,), "stamp factor")
+        if tuple(self._i32(stamps["radius_voxels"], rows, "stamp radius_voxels").shape) != (rows,):
+            raise ValueError(f"stamp radius_voxels: int32 ({rows},)")
+        return [self.be.ptr(stamps[k]) for k in ("centres", "radius", "radius_voxels", "factor")]
+
+    def mission_goal(self, mp: MissionParams, state, now, pos, waypoints, labels, resolution: float = 1.0, goal=None, stamps=None):
+        """se3mpc_mission_goal_*: GlobalMissionPlanner.get_current_goal for B drones.  state: the mission records (B, 4), updated in place; now:
+        float64 (B,), the wall clock of the call; pos (B, 3) float32 or float64; waypoints, labels: the table (:meth:`_waypoints`); resolution: of
+        the field the stamps are meant for.  goal, stamps: outputs of an earlier call to be written again.
+        -> dict(goal (B, 3) of pos's dtype, stamps = the B-row table :meth:`ufield_stamp` takes: radius_voxels -1 where nothing was stamped)."""
+        B = pos.shape[0]
+        suf = self.be.suffix(pos)
+        self._rows3(pos, B, "pos", suf)
+        self._clock(now, B)
+        self._mission_record(state, B)
+        table = self._waypoints(waypoints, labels, B)
+        goal = self.be.empty((B, 3), suf) if goal is None else self._rows3(goal, B, "goal", suf)
+        stamps = self.mission_stamps(B) if stamps is None else stamps
+        self.lib.loop_call("mission_goal", suf, mp, B, self.be.ptr(now), self.be.ptr(pos), self.be.ptr(state), *table, float(resolution), self.be.ptr(goal),
+                           *self._stamps(stamps, B), self.be.stream())
+        return dict(goal=goal, stamps=stamps)
+
+    def monte_carlo_mission(self, params: Params, cp: ControllerParams, sp: SimulatorParams, mp: MissionParams, state, mission_state, time, pos, vel,
+                            att, omega, waypoints, labels, cycles: int, substeps: int, sim_dt: float, epoch: float = 1000.0, resolution: float = 1.0,
+                            wind=None, first_cycle: int = 0, goal=None, want_stamps: bool = False, want_last_plan: bool = False):
+        """se3mpc_monte_carlo_mission_*: `cycles` x (mission goal at now = the drone's clock + epoch, solve towards it, `substeps` control + simulator
+        steps) for B drones in ONE launch, in place on (state, mission_state, time, pos, vel, att, omega).  The plan's stamps count from
+        `first_cycle`: a second call with first_cycle = the cycles already flown continues a run on the same operands.
+        -> dict(overflowed as :meth:`monte_carlo`, goal (B, 3) = the last cycle's, stamps = the (cycles * B)-row log of the global plans' stamps
+        in the chain's order if `want_stamps` else None, x, accelerations, info of the last cycle's plan if asked for)."""
+        B = pos.shape[0]
+        suf = self.be.suffix(pos)
+        self._drone_state(B, suf, pos, vel, att, omega)
+        self._ctrl_state(state, B)
+        self._mission_record(mission_state, B)
+        self._clock(time, B, "time")
+        w_stride = self._wind(wind, B, suf)
+        table = self._waypoints(waypoints, labels, B)
+        if goal is None:
+            goal = self.be.empty((B, 3), suf)
+            goal[...] = 0
+        self._rows3(goal, B, "goal", suf)
+        N = params.horizon
+        rows = max(int(cycles), 0) * B
+        stamps = self.mission_stamps(rows) if want_stamps else None
+        over = self.be.empty((1,), "i32")
+        X = self.be.empty((B, 9 * N), suf) if want_last_plan else None
+        acc = self.be.empty((B, N, 3), suf) if want_last_plan else None
+        info = self.be.empty((B * INFO_DTYPE.itemsize,), "u8") if want_last_plan else None
+        self.lib.loop_call("monte_carlo_mission", suf, params, cp, sp, mp, B, int(cycles), int(substeps), float(sim_dt), int(first_cycle), float(epoch), *table,
+                           float(resolution), self.be.ptr(wind), w_stride, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel), self.be.ptr(att),
+                           self.be.ptr(omega), self.be.ptr(state), self.be.ptr(mission_state), self.be.ptr(goal),
+                           *(self._stamps(stamps, rows) if want_stamps else [0, 0, 0, 0]), self.be.ptr(X), self.be.ptr(acc), self.be.ptr(info),
+                           self.be.ptr(over), self.be.stream())
+        return dict(overflowed=over, goal=goal, stamps=stamps, x=X, accelerations=acc, info=info)
 
     # ------------------------------------------------------------------ problem layout
     def solve(self, params: Params, p0, v0, goal, x0=None, want_trajectory=True, out=None):

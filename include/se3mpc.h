@@ -1203,6 +1203,105 @@ int se3mpc_monte_carlo_edge_f64(const se3mpc_params* p, const se3mpc_onboard_par
                                 double* ring, double* ring_time, double* latency_state, int32_t* zero_thrust_steps, double* X_last,
                                 double* acc_last, se3mpc_solve_info* info_last, int32_t* overflowed, void* stream);
 
+/* ------------------------------------------------------------------ mission layer: the goal source
+ * GlobalMissionPlanner.get_current_goal (src/dart_planner/planning/global_mission_planner.py:182-224, "mission.py" below), the call that
+ * produces the goal of every plan: a phase machine per drone -- phase, waypoint index, time of the last global plan -- unit-stripped and
+ * reproduced with its quirks.  The wall clock the class reads (time.time(), :195) is the operand `now`.  Not reproduced: the np.random
+ * parts (the simulated regions of :433-442 and the placeholder of :462-465, read only by the non-empty branch of _plan_exploration_goal)
+ * and PlaceholderNeuralScene. */
+typedef struct se3mpc_mission_params {
+  double safe_altitude;          /* takeoff goal altitude, 5.0                                  (mission.py:256)   */
+  double takeoff_band;           /* takeoff complete at z >= safe_altitude - band, 0.5          (:261)             */
+  double waypoint_reach;         /* a waypoint is reached at distance < this, 2.0               (:322)             */
+  double safety_margin;          /* GlobalMissionConfig.safety_margin, 2.0                      (:48, :376)        */
+  double landing_pad_lift;       /* approach a landing pad from this far above, 3.0             (:380)             */
+  double landing_step;           /* LANDING: goal z = max(floor, z - step), 1.0 and 0.5         (:347)             */
+  double landing_floor;
+  double emergency_step;         /* EMERGENCY: goal z = max(floor, z - step), 2.0 and 0.0       (:358)             */
+  double emergency_floor;
+  double emergency_altitude;     /* a global plan below this altitude outside LANDING: EMERGENCY, 0.5   (:454)     */
+  double global_replan_period;   /* 1 / global_replan_frequency, 1.0                            (:60, :198)        */
+  double exploration_base;       /* radius of the first exploration goal, 10.0                  (:284)             */
+  double exploration_radius;     /* GlobalMissionConfig.exploration_radius, 50.0                (:46)              */
+  double stamp_radius;           /* reduce_uncertainty_around_position of a global plan: 3.0, 0.2   (:411-413)     */
+  double stamp_factor;
+  int32_t use_neural_scene;      /* GlobalMissionConfig.use_neural_scene                        (:51)              */
+  int32_t reserved;
+} se3mpc_mission_params;
+
+/* MissionPhase (mission.py:17-25) in its order; the semantic labels _apply_semantic_reasoning tells apart (:370-384). */
+enum { SE3MPC_MISSION_TAKEOFF = 0, SE3MPC_MISSION_EXPLORATION = 1, SE3MPC_MISSION_MAPPING = 2, SE3MPC_MISSION_NAVIGATION = 3,
+       SE3MPC_MISSION_LANDING = 4, SE3MPC_MISSION_EMERGENCY = 5 };
+enum { SE3MPC_LABEL_OTHER = 0, SE3MPC_LABEL_OBSTACLE = 1, SE3MPC_LABEL_LANDING_PAD = 2, SE3MPC_LABEL_DOORWAY = 3 };
+
+/* Mutable planner members (mission.py:95-97, :156), SE3MPC_MISSION_STATE_WORDS doubles per drone: [0] current_phase (a code above), [1]
+ * current_waypoint_index, [2] last_global_plan_time, [3] global plans made (= the scene's update count with use_neural_scene).  The caller
+ * may write EXPLORATION or MAPPING into [0]: nothing in the reference enters them either.  A phase word outside [0, 5] returns the position
+ * as the goal (:222-224); an index below 0 or NaN reads as 0. */
+#define SE3MPC_MISSION_STATE_WORDS 4
+
+/* The reference's literals. */
+int se3mpc_mission_default_params(se3mpc_mission_params* out);
+/* SE3MPC_ERR_NULL; a non-finite value or a period that is not positive: SE3MPC_ERR_PARAM. */
+int se3mpc_check_mission_params(const se3mpc_mission_params* mp);
+/* TAKEOFF, index 0, last_global_plan_time 0.0, no plan made (mission.py:95-97, :156) for B drones. */
+int se3mpc_mission_reset(int B, double* mission_state, void* stream);
+
+/* get_current_goal for B drones, one per lane.  now [B]: the wall clock of each call; pos [B][3]; mission_state [B][SE3MPC_MISSION_STATE_WORDS]
+ * in / out.  waypoints: float64 [W][3] rows shared by all drones (wp_stride 0) or per drone (wp_stride >= 3 W doubles from drone to drone);
+ * labels int32 [W] under the same rule (label_stride 0 or >= W); W = 0: no waypoints (both may be NULL).  In order (mission.py:195-220): if
+ * now - last_global_plan_time > global_replan_period, the global planning step -- below emergency_altitude and outside LANDING the phase
+ * becomes EMERGENCY (:450-458), the plan count goes up, last_global_plan_time = now -- then the goal of the phase: TAKEOFF :254-265,
+ * NAVIGATION and MAPPING :302-341 with _apply_semantic_reasoning :362-386, LANDING :343-353, EMERGENCY :355-360, EXPLORATION on its
+ * empty-region branch :279-294 with nothing explored yet.  Every decision and all arithmetic in double on (double)pos; goal [B][3] is rounded
+ * to the IO type once, on the store.  The stamp of the global planning step (:409-413) is row b of a table in the operand form of
+ * se3mpc_ufield_stamp: stamp_centres [B][3] = the position, stamp_radius [B], stamp_radius_voxels [B] = (int)(stamp_radius / resolution),
+ * stamp_factor [B]; a drone that made no global plan, and every drone without use_neural_scene, gets radius = -1 and radius_voxels = -1,
+ * which se3mpc_ufield_stamp skips.
+ * Argument rules: NULL params: SE3MPC_ERR_NULL; params se3mpc_check_mission_params rejects: its code; B outside [0, 2^30], W outside
+ * [0, 2^20], a stride that is neither 0 nor at least a table: SE3MPC_ERR_SHAPE; with use_neural_scene a resolution that is not finite and
+ * positive: SE3MPC_ERR_PARAM; B = 0: a no-op; then any NULL operand (the two tables only when W > 0): SE3MPC_ERR_NULL.  A rejected call sets
+ * se3mpc_last_error and launches nothing. */
+int se3mpc_mission_goal_f32(const se3mpc_mission_params* mp, int B, const double* now, const float* pos, double* mission_state,
+                            const double* waypoints, long long wp_stride, const int32_t* labels, long long label_stride, int W,
+                            double resolution, float* goal, double* stamp_centres, double* stamp_radius, int32_t* stamp_radius_voxels,
+                            double* stamp_factor, void* stream);
+int se3mpc_mission_goal_f64(const se3mpc_mission_params* mp, int B, const double* now, const double* pos, double* mission_state,
+                            const double* waypoints, long long wp_stride, const int32_t* labels, long long label_stride, int W,
+                            double resolution, double* goal, double* stamp_centres, double* stamp_radius, int32_t* stamp_radius_voxels,
+                            double* stamp_factor, void* stream);
+
+/* se3mpc_monte_carlo_* flying waypoint missions in ONE launch: for each of B drones, `cycles` times { se3mpc_mission_goal_*
+ * on the drone's position with now = its clock + epoch; se3mpc_solve_* towards that goal; `substeps` x the step of se3mpc_closed_loop_*
+ * against the fresh plan, whose row k is stamped ((first_cycle + cycle) * substeps * sim_dt) + k * params->dt }.  The same code as the three
+ * entry points it fuses, hence the same bits as alternating them (ClosedLoopMonteCarlo.run_mission).  All cross-cycle state is the caller's,
+ * so a second call with first_cycle = the cycles already flown continues a run bit for bit.  mp, waypoints .. resolution and mission_state
+ * as se3mpc_mission_goal_*; wind .. state, X_last, acc_last, info_last and overflowed as se3mpc_monte_carlo_*; goal [B][3]: out, the last
+ * cycle's goal (with cycles = 0 it stays as it is).  The stamps of the global planning steps are not applied -- they are ordered writes to
+ * a grid all drones share, and the phase machine never reads it -- but logged: log_centres [cycles][B][3], log_radius, log_radius_voxels,
+ * log_factor [cycles][B], rows as se3mpc_mission_goal_* writes them, cycle-major as the chain makes them; one se3mpc_ufield_stamp call with
+ * S = cycles * B applies them.  All four NULL: no log.
+ * Argument rules, in this order: a NULL parameter struct: SE3MPC_ERR_NULL; parameters that se3mpc_check_params, se3mpc_closed_loop_* or
+ * se3mpc_check_mission_params reject: their codes; parameters without a goal (has_goal == 0): SE3MPC_ERR_PARAM; B, cycles, substeps or
+ * first_cycle < 0, horizon > 64, (first_cycle + cycles) * substeps beyond an int, cycles * B beyond 2^30: SE3MPC_ERR_SHAPE; a non-finite
+ * sim_dt or epoch: SE3MPC_ERR_PARAM; the wind and table rules of the entry points above; B = 0: a no-op; then a NULL time, pos, vel, att,
+ * omega, state, mission_state, goal or overflowed, a NULL table when W > 0, a log of which only a part is there: SE3MPC_ERR_NULL.  A rejected
+ * call launches nothing; overflowed is zeroed on the stream before the launch. */
+int se3mpc_monte_carlo_mission_f32(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp,
+                                   const se3mpc_mission_params* mp, int B, int cycles, int substeps, double sim_dt, int first_cycle,
+                                   double epoch, const double* waypoints, long long wp_stride, const int32_t* labels, long long label_stride,
+                                   int W, double resolution, const float* wind, long long wind_stride, double* time, float* pos, float* vel,
+                                   float* att, float* omega, double* state, double* mission_state, float* goal, double* log_centres,
+                                   double* log_radius, int32_t* log_radius_voxels, double* log_factor, float* X_last, float* acc_last,
+                                   se3mpc_solve_info* info_last, int32_t* overflowed, void* stream);
+int se3mpc_monte_carlo_mission_f64(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp,
+                                   const se3mpc_mission_params* mp, int B, int cycles, int substeps, double sim_dt, int first_cycle,
+                                   double epoch, const double* waypoints, long long wp_stride, const int32_t* labels, long long label_stride,
+                                   int W, double resolution, const double* wind, long long wind_stride, double* time, double* pos,
+                                   double* vel, double* att, double* omega, double* state, double* mission_state, double* goal,
+                                   double* log_centres, double* log_radius, int32_t* log_radius_voxels, double* log_factor, double* X_last,
+                                   double* acc_last, se3mpc_solve_info* info_last, int32_t* overflowed, void* stream);
+
 /* The closed-loop MPPI Monte-Carlo on the edge loop in ONE launch: se3mpc_mppi_closed_loop_* with the act phase of
  * se3mpc_monte_carlo_edge_*.  One workgroup of min(S, 256) lanes per drone; for each of B drones, `cycles` times { plan, hand over, clearance
  * and warm start as se3mpc_mppi_closed_loop_* (the same code, hence the same bits: Philox stream index_base + b, iteration number iter_base +

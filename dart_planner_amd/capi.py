@@ -17,6 +17,7 @@ DEFAULT_LIBRARY = os.path.join(_HERE, "libse3mpc.so")
 SE3MPC_MAX_HORIZON = 64
 SE3MPC_MAX_CORRECTIONS = 10
 SE3MPC_MAX_SPHERES = 256
+SE3MPC_MAX_TRACKS = 16
 
 STATUS_NAMES = {0: "SE3MPC_OK", -1: "SE3MPC_ERR_NULL", -2: "SE3MPC_ERR_HORIZON", -3: "SE3MPC_ERR_SHAPE",
                 -4: "SE3MPC_ERR_PARAM", -5: "SE3MPC_ERR_WORKSPACE", -6: "SE3MPC_ERR_LAUNCH",
@@ -340,6 +341,8 @@ _TYPED_API = {
     "population_sums": (False, [_I, _I, _I, _P, _P, _D, _P, _D, _P, _P, _P]),
     "mppi": (True, [_I, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _P]),
     "mppi_moving": (True, [_I, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _D, _I, _D, _P, _P, _P, _P]),
+    "mppi_tracks": (True, [_I, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _D, _I, _P, _I, C.c_longlong, _D,
+                           _P, _P, _P, _P]),
     "mppi_split": (True, [_I, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _I, _P, C.c_size_t,
                           _P]),
     "mppi_samples": (True, [_I, _I, _I, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _I, _P, _P, _P]),
@@ -414,6 +417,11 @@ _LOOP_TYPED_API = {
                          _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mppi_closed_loop_moving": [_PP, _CP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, _D, _I,
                                 _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mppi_closed_loop_tracks": [_PP, _CP, _SP, _I, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, _D, _I,
+                                _P, _I, _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mppi_closed_loop_swarm_intent": [_PP, _CP, _SP, _I, _I, _I, _D, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P,
+                                      _P, _P, _D, _I, _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
+    "swarm_intent": [_PP, _I, _P, _P, _P, _P, _P],
     "mppi_closed_loop_swarm": [_PP, _CP, _SP, _I, _I, _I, _D, _I, _I, _D, C.c_uint32, _I, _I, _I, _D, _D, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P,
                                _D, _I, _D, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P],
     "swarm_separation": [_I, _I, _P, _P, _P, _P],
@@ -450,6 +458,7 @@ _PLAIN_API = {
     "se3mpc_population_workspace": (C.c_int, [_I, _I]),
     "se3mpc_mppi_split_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "se3mpc_mppi_swarm_workspace_bytes": (C.c_size_t, [_I, _I]),
+    "se3mpc_mppi_swarm_intent_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
 }
 
 
@@ -549,6 +558,9 @@ class Library:
 
     def mppi_swarm_workspace_bytes(self, B: int, elem_size: int) -> int:
         return self._dll.se3mpc_mppi_swarm_workspace_bytes(B, elem_size)
+
+    def mppi_swarm_intent_workspace_bytes(self, B: int, horizon: int, elem_size: int) -> int:
+        return self._dll.se3mpc_mppi_swarm_intent_workspace_bytes(B, horizon, elem_size)
 
     def key_index(self, key: int) -> int:
         return self._dll.se3mpc_key_index(C.c_uint64(key))

@@ -22,6 +22,7 @@ same planner: a latency buffer between the drone's state and its controller, and
 GlobalMissionPlanner.get_current_goal on the drone's own position (``se3mpc_mission_goal_*``, ``se3mpc_monte_carlo_mission_*``)
 where every other method holds one goal for the whole run.
 """
+import functools
 import math
 from typing import Optional
 
@@ -433,7 +434,7 @@ class ClosedLoopMonteCarlo:
     def run_mppi_fused(self, p0, v0, goal, cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float,
                        temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None,
                        nominal=None, log: bool = False, smoother=None, mixer=None, motor_health=None, sphere_velocities=None,
-                       sphere_t0: float = 0.0):
+                       sphere_t0: float = 0.0, tracks=None):
         """:meth:`run_mppi` in ONE launch: every drone's `cycles` planning cycles inside one kernel, the plan never leaving the chip.  Same
         code, same bits as :meth:`run_mppi`, same arguments and the same shift rule (shift=None: ``floor(substeps * sim_dt / params.dt +
         0.5)`` clipped to [0, N]).  `log` keeps the last cycle's plan only: logs = [dict(plan_last, trace, cost)] with one entry.
@@ -443,15 +444,19 @@ class ClosedLoopMonteCarlo:
         At 4096 drones it is 17 - 27 % SLOWER than that chain (the kernel holds the controller's registers, so the MPPI phase runs at three
         (float32) / two (float64) wavefronts per SIMD instead of four, and one lane per workgroup flies while the others wait): for thousands of
         drones drive the chain (``tools/gpu_probe_mppi_closed_loop.py``, ``chain_form``) unless the clearance output is what you need.
-        sphere_velocities, sphere_t0: as in :meth:`run_mppi` -- the table advances through all `cycles` inside the one kernel."""
+        sphere_velocities, sphere_t0: as in :meth:`run_mppi` -- the table advances through all `cycles` inside the one kernel.
+        tracks: None, or (cycles, B, N, Kt, 4) rows (x, y, z, r): spheres with a predicted path, renewed every cycle, behind the moving ones
+        (``se3mpc_mppi_closed_loop_tracks_*``): row [c][b][k][j] is sphere j at the time of the state before step k of
+        drone b's plan in cycle c.  The clearance does not see them."""
         self._no_smoother(smoother, "run_mppi_fused")
         self._no_mixer(mixer, motor_health, "run_mppi_fused")
         st, sm, fl = self._start(p0, v0)
         U = self._mppi_start(p0, nominal)
         sh = self.resolve_shift(substeps, sim_dt, shift)
-        out = self.ops.mppi_closed_loop(self.params, self.controller, self.simulator, st, *fl, goal, U, cycles, substeps, sim_dt,
-                                        n_samples, iters, sigma, temperature, seed=seed, cycle_base=0, shift=sh, spheres=spheres,
-                                        obstacle_weight=obstacle_weight, wind=wind, want_plan=log, sphere_vel=sphere_velocities, sphere_t0=sphere_t0)
+        entry = self.ops.mppi_closed_loop if tracks is None else functools.partial(self.ops.mppi_closed_loop_tracks, tracks=tracks)
+        out = entry(self.params, self.controller, self.simulator, st, *fl, goal, U, cycles, substeps, sim_dt,
+                    n_samples, iters, sigma, temperature, seed=seed, cycle_base=0, shift=sh, spheres=spheres,
+                    obstacle_weight=obstacle_weight, wind=wind, want_plan=log, sphere_vel=sphere_velocities, sphere_t0=sphere_t0)
         logs = [dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"])] if log else []
         return self._result(st, sm, fl, logs=logs, U=U, cost=out["cost"], trace=out["trace"], clearance=out["clearance"])
 
@@ -459,7 +464,7 @@ class ClosedLoopMonteCarlo:
                        temperature: float, seed: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None, shift: Optional[int] = None,
                        nominal=None, log: bool = False, smoother=None, mixer=None, motor_health=None, sphere_velocities=None,
                        sphere_t0: float = 0.0, swarm_size: int = 1, neighbours: int = 0, mate_radius: float = 0.0,
-                       want_neighbours: bool = False):
+                       want_neighbours: bool = False, share_plans: bool = False):
         """:meth:`run_mppi_fused` for swarms (``se3mpc_mppi_closed_loop_swarm_*``): the B drones are B / `swarm_size` swarms
         of `swarm_size` consecutive drones, and every drone plans around its `neighbours` nearest swarm-mates as spheres of radius
         `mate_radius` that keep the velocity they have when the cycle starts (`obstacle_weight` weighs them like the shared `spheres`).
@@ -467,7 +472,9 @@ class ClosedLoopMonteCarlo:
         ``se3mpc_swarm_separation_*`` on the final state.  -> what :meth:`run_mppi_fused` returns (clearance: against the shared spheres
         only), plus separation (B,) = the minimum over the cycle starts and the final state of the distance to the nearest mate, and
         neighbours (B, `neighbours`) int32 = the mates chosen in the last cycle (None unless `want_neighbours`).  With swarm_size = 1 it is
-        :meth:`run_mppi_fused`, bit for bit.  There is no staged or edge form."""
+        :meth:`run_mppi_fused`, bit for bit.  There is no staged or edge form.
+        share_plans: the mates are shown as their plans, not as their velocities (``se3mpc_mppi_closed_loop_swarm_intent_*``, DESIGN.md
+        5.8h): a mate's sphere at step k of the horizon is where the rollout of its own nominal puts it; `neighbours` <= 16."""
         self._no_smoother(smoother, "run_mppi_swarm")
         self._no_mixer(mixer, motor_health, "run_mppi_swarm")
         st, sm, fl = self._start(p0, v0)
@@ -477,7 +484,7 @@ class ClosedLoopMonteCarlo:
                                               n_samples, iters, sigma, temperature, swarm_size=swarm_size, neighbours=neighbours,
                                               mate_radius=mate_radius, seed=seed, cycle_base=0, shift=sh, spheres=spheres,
                                               obstacle_weight=obstacle_weight, wind=wind, want_plan=log, sphere_vel=sphere_velocities,
-                                              sphere_t0=sphere_t0, want_neighbours=want_neighbours)
+                                              sphere_t0=sphere_t0, want_neighbours=want_neighbours, share_plans=share_plans)
         sep = self.ops.swarm_separation(fl[1], fl[2], swarm_size, separation=out["separation"])
         logs = [dict(plan_last=out["plan_last"], trace=out["trace"], cost=out["cost"])] if log else []
         return self._result(st, sm, fl, logs=logs, U=U, cost=out["cost"], trace=out["trace"], clearance=out["clearance"], separation=sep,

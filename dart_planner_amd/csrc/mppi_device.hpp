@@ -66,8 +66,19 @@ struct CtxMotion<R, true> {
   const R* stime;   // LDS [N]: tR_k = (R)tau_k, the time of the state before step k on the table's clock
 };
 
-template <typename R, bool MOVING = false>
-struct Ctx : CtxMotion<R, MOVING> {
+// What TRACKED spheres add behind the moving table (se3mpc_mppi_tracks_*): a slab of centres given per step of the horizon.
+// Again through an empty base: Ctx<R> and Ctx<R, true> are the structs they were.
+template <typename R, bool TRACKED>
+struct CtxTracks {};
+template <typename R>
+struct CtxTracks<R, true> {
+  const R* trk;     // LDS [N][Kt][4] = (x, y, z, (r + margin)^2): row [k][j] = tracked sphere j at the state before step k
+  int Kt;
+};
+
+template <typename R, bool MOVING = false, bool TRACKED = false>
+struct Ctx : CtxMotion<R, MOVING>, CtxTracks<R, TRACKED> {
+  static_assert(MOVING || !TRACKED, "the tracked rows come behind a moving table");
   DevParams<R> q;
   uint32_t key0, key1, qi, g;
   const R* U;       // LDS [3N]
@@ -79,8 +90,8 @@ struct Ctx : CtxMotion<R, MOVING> {
 
 // Sample s at step k: the noise (raw words / normals optional) and the clipped thrust.  The one expression mppi_samples_kernel and
 // the fused kernel share, so the two agree bit for bit.
-template <typename R, bool MOVING>
-__device__ __forceinline__ void draw(const Ctx<R, MOVING>& c, const R* Uk, uint32_t s, int k, R sig, R t[3], uint32_t* raw = nullptr, R* nrm = nullptr) {
+template <typename R, bool MOVING, bool TRACKED>
+__device__ __forceinline__ void draw(const Ctx<R, MOVING, TRACKED>& c, const R* Uk, uint32_t s, int k, R sig, R t[3], uint32_t* raw = nullptr, R* nrm = nullptr) {
   uint32_t x[4] = {c.qi, s, c.g, (uint32_t)k};
   philox4x32_10(x, c.key0, c.key1);
   R n[3];
@@ -98,9 +109,11 @@ struct Roll {
 };
 
 // One step of the forward sweep (planner.py:449-460 solved forward, the objective of :516-550, the sphere penalty on P_k).  MOVING: sphere
-// j's centre at step k is c_j + v_j * tR_k (one multiply-add per axis; v_j = 0 leaves c_j exactly), then the same expression.
-template <typename R, bool MOVING>
-__device__ __forceinline__ void roll_step(const Ctx<R, MOVING>& c, Roll<R>& r, int k, const R t[3]) {
+// j's centre at step k is c_j + v_j * tR_k (one multiply-add per axis; v_j = 0 leaves c_j exactly), then the same expression.  TRACKED: behind
+// the K moving rows the Kt rows of step k of the slab, their centres read as they stand (no time arithmetic), the same expression, pen
+// summed on in rising index.
+template <typename R, bool MOVING, bool TRACKED>
+__device__ __forceinline__ void roll_step(const Ctx<R, MOVING, TRACKED>& c, Roll<R>& r, int k, const R t[3]) {
   const DevParams<R>& q = c.q;
   R acc[3];
 #pragma unroll
@@ -127,6 +140,16 @@ __device__ __forceinline__ void roll_step(const Ctx<R, MOVING>& c, Roll<R>& r, i
     const R h = fmax((R)0, -cc);
     r.pen += h * h;
   }
+  if constexpr (TRACKED) {
+    const R* row = c.trk + (size_t)4 * c.Kt * k;
+    for (int j = 0; j < c.Kt; ++j) {
+      const R* s4 = row + 4 * j;
+      const R dx = r.p[0] - s4[0], dy = r.p[1] - s4[1], dz = r.p[2] - s4[2];
+      const R cc = dz * dz + (dy * dy + (dx * dx - s4[3]));
+      const R h = fmax((R)0, -cc);
+      r.pen += h * h;
+    }
+  }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     r.p[a] = r.p[a] + r.v[a] * q.dt + q.half_dt2 * acc[a];
@@ -146,8 +169,8 @@ __device__ __forceinline__ void roll_state_step(const DevParams<R>& q, R p[3], R
   }
 }
 
-template <typename R, bool MOVING>
-__device__ __forceinline__ Roll<R> roll_begin(const Ctx<R, MOVING>& c) {
+template <typename R, bool MOVING, bool TRACKED>
+__device__ __forceinline__ Roll<R> roll_begin(const Ctx<R, MOVING, TRACKED>& c) {
   Roll<R> r;
 #pragma unroll
   for (int a = 0; a < 3; ++a) { r.p[a] = c.p0[a]; r.v[a] = c.v0[a]; }
@@ -155,8 +178,8 @@ __device__ __forceinline__ Roll<R> roll_begin(const Ctx<R, MOVING>& c) {
   return r;
 }
 
-template <typename R, bool MOVING>
-__device__ __forceinline__ R roll_total(const Ctx<R, MOVING>& c, const Roll<R>& r) {
+template <typename R, bool MOVING, bool TRACKED>
+__device__ __forceinline__ R roll_total(const Ctx<R, MOVING, TRACKED>& c, const Roll<R>& r) {
   const DevParams<R>& q = c.q;
   R cost = q.wv * r.sv + q.wa * r.sa + q.wT * r.st;
   if (q.has_goal) cost += q.wp * (r.sp + r.sterm) + q.term * q.wp * r.sterm;
@@ -164,8 +187,8 @@ __device__ __forceinline__ R roll_total(const Ctx<R, MOVING>& c, const Roll<R>& 
 }
 
 // Cost of sample s (NOISE) or of the nominal as it stands (!NOISE: no draw, no clip -- the final evaluation)
-template <typename R, bool NOISE, bool MOVING>
-__device__ __forceinline__ R sample_cost(const Ctx<R, MOVING>& c, uint32_t s, R sig) {
+template <typename R, bool NOISE, bool MOVING, bool TRACKED>
+__device__ __forceinline__ R sample_cost(const Ctx<R, MOVING, TRACKED>& c, uint32_t s, R sig) {
   Roll<R> r = roll_begin(c);
   for (int k = 0; k < c.q.N; ++k) {
     R t[3];
@@ -205,6 +228,18 @@ __host__ __device__ inline MovingLds moving_lds_layout(int N, int K, int W, size
   return m;
 }
 
+// Behind an image whose end the caller names (the planner's moving image, or a closed loop's), the kernels of tracked spheres keep
+// (DESIGN.md 5.8h): trk [N][Kt][4] R
+struct TrackLds {
+  size_t trk, total;
+};
+__host__ __device__ inline TrackLds track_lds_layout(size_t behind, int N, int Kt, size_t esz) {
+  TrackLds t;
+  t.trk = align16(behind);
+  t.total = align16(t.trk + (size_t)4 * N * Kt * esz);
+  return t;
+}
+
 // The image as pointers
 template <typename R>
 struct LdsView {
@@ -222,7 +257,8 @@ __device__ __forceinline__ LdsView<R> lds_view(unsigned char* lds_raw, const Lds
   return v;
 }
 
-// The sphere table into LDS as (cx, cy, cz, (r + margin)^2); the caller's __syncthreads() publishes it
+// The sphere table into LDS as (cx, cy, cz, (r + margin)^2); the caller's __syncthreads() publishes it.  (A slab of tracked spheres
+// [N][Kt][4] is a table of N * Kt rows.)
 template <typename R>
 __device__ __forceinline__ void stage_spheres(const DevParams<R>& q, const R* __restrict__ spheres, int K, R* sph) {
   for (int i = (int)threadIdx.x; i < 4 * K; i += (int)blockDim.x) {
@@ -231,11 +267,11 @@ __device__ __forceinline__ void stage_spheres(const DevParams<R>& q, const R* __
   }
 }
 
-// (MOVING: the caller sets svel and stime)
-template <typename R, bool MOVING = false>
-__device__ __forceinline__ Ctx<R, MOVING> load_ctx(const DevParams<R>& q, int ld, int p, uint32_t key0, uint32_t key1, uint32_t qi, const R* p0,
+// (MOVING: the caller sets svel and stime; TRACKED: trk and Kt)
+template <typename R, bool MOVING = false, bool TRACKED = false>
+__device__ __forceinline__ Ctx<R, MOVING, TRACKED> load_ctx(const DevParams<R>& q, int ld, int p, uint32_t key0, uint32_t key1, uint32_t qi, const R* p0,
                                                    const R* v0, const R* goal, const R* U, const R* sph, int K, R w_obs) {
-  Ctx<R, MOVING> c;
+  Ctx<R, MOVING, TRACKED> c;
   c.q = q; c.key0 = key0; c.key1 = key1; c.qi = qi; c.g = 0; c.U = U; c.sph = sph; c.K = K; c.w_obs = w_obs;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -251,8 +287,8 @@ __device__ __forceinline__ Ctx<R, MOVING> load_ctx(const DevParams<R>& q, int ld
 // wavefront partials folded in wavefront order, chunks folded in chunk order with the streaming rescale.  Returns the minimum cost m of
 // the range (+inf when every cost is NaN) and leaves acc[r] = sum_s w_s T_s[r] (r < 3N), acc[3N] = sum_s w_s, w_s = exp(-(c_s - m) / lambda),
 // in LDS, visible to the whole workgroup.
-template <typename R, bool MOVING>
-__device__ __forceinline__ double weighted_pass(const Ctx<R, MOVING>& c, const R* U, int s_lo, int count, R sigma, double inv_lam, double* acc, double* part,
+template <typename R, bool MOVING, bool TRACKED>
+__device__ __forceinline__ double weighted_pass(const Ctx<R, MOVING, TRACKED>& c, const R* U, int s_lo, int count, R sigma, double inv_lam, double* acc, double* part,
                                                 double* red) {
   const int N = c.q.N, rows = 3 * N, NT = (int)blockDim.x, W = NT / kWave;
   const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
@@ -327,8 +363,8 @@ __device__ __forceinline__ void shift_nominal(const DevParams<R>& q, R* U, R* tm
 }
 
 // Cost and argmin key of the nominal as it stands, written by lane 0 of the calling wavefront (the tail of every MPPI entry point)
-template <typename R, bool MOVING>
-__device__ __forceinline__ void write_nominal_cost(const Ctx<R, MOVING>& c, int p, uint32_t index_base, R* cost_out, uint64_t* keys) {
+template <typename R, bool MOVING, bool TRACKED>
+__device__ __forceinline__ void write_nominal_cost(const Ctx<R, MOVING, TRACKED>& c, int p, uint32_t index_base, R* cost_out, uint64_t* keys) {
   const R cf = sample_cost<R, false>(c, 0u, (R)0);
   if ((threadIdx.x & (kWave - 1)) == 0) {
     cost_out[p] = cf;
@@ -375,6 +411,16 @@ static int check_mppi_args(const char* fn, const se3mpc_params* p, int nprob, in
 static int check_moving_args(const char* fn, int K, const void* sphere_vel, double sphere_t0) {
   if (!std::isfinite(sphere_t0)) return fail(SE3MPC_ERR_PARAM, "sphere_t0 must be finite", fn);
   if (K > 0 && sphere_vel == nullptr) return fail(SE3MPC_ERR_NULL, "sphere_vel is NULL with K > 0", fn);
+  return SE3MPC_OK;
+}
+
+// ... and what the entries of tracked spheres add (se3mpc_mppi_tracks_*, se3mpc_mppi_closed_loop_tracks_*), after the rules above
+static int check_track_args(const char* fn, int K, int Kt, const void* tracks, long long track_stride, int N) {
+  if (Kt < 0 || Kt > SE3MPC_MAX_TRACKS) return fail(SE3MPC_ERR_SHAPE, "Kt outside [0, SE3MPC_MAX_TRACKS]", fn);
+  if (K + Kt > SE3MPC_MAX_SPHERES) return fail(SE3MPC_ERR_SHAPE, "K + Kt > SE3MPC_MAX_SPHERES", fn);
+  if (Kt > 0 && track_stride != 0 && track_stride < (long long)4 * N * Kt)
+    return fail(SE3MPC_ERR_SHAPE, "track_stride must be 0 or >= 4 * horizon * Kt", fn);
+  if (Kt > 0 && tracks == nullptr) return fail(SE3MPC_ERR_NULL, "tracks is NULL with Kt > 0", fn);
   return SE3MPC_OK;
 }
 

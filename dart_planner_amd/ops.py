@@ -18,7 +18,7 @@ import ctypes as _C
 import numpy as np
 
 from .capi import (CONTROLLER_STATE_WORDS, LATENCY_MAX_DEPTH, LATENCY_STATE_WORDS, MISSION_STATE_WORDS, MIXER_STATE_WORDS, ONBOARD_STATE_WORDS,
-                   SMOOTHER_STATE_WORDS, SE3MPC_MAX_SPHERES, ControllerParams, Library, MissionParams, MixerParams, OnboardParams, Params,
+                   SMOOTHER_STATE_WORDS, SE3MPC_MAX_SPHERES, SE3MPC_MAX_TRACKS, ControllerParams, Library, MissionParams, MixerParams, OnboardParams, Params,
                    SimulatorParams, SmootherParams, SolveInfo, UFieldDesc, get_library)
 
 INFO_DTYPE = np.dtype([("fun", "<f8"), ("nit", "<i4"), ("nfev", "<i4"), ("status", "<i4"), ("task", "<i4")])
@@ -114,6 +114,16 @@ class Ops:
         if sphere_vel.ndim != 2 or tuple(sphere_vel.shape) != (K, 3) or self.be.suffix(sphere_vel) != suf:
             raise ValueError(f"sphere_vel: expected ({K}, 3) {suf} beside the sphere table, got {tuple(sphere_vel.shape)}")
         return (self.be.ptr(sphere_vel if K else None), float(sphere_t0))
+
+    def _tracks(self, tracks, lead: tuple, N: int, K: int, suf) -> int:
+        """A slab of tracked spheres ``lead`` + (N, Kt, 4) rows (x, y, z, r) of the call's dtype beside a moving table of K rows -> Kt."""
+        self.be.check(tracks, "tracks")
+        nl = len(lead)
+        if (tracks.ndim != nl + 3 or tuple(tracks.shape[:nl]) != tuple(lead) or tracks.shape[nl] != N or tracks.shape[nl + 2] != 4
+                or tracks.shape[nl + 1] > SE3MPC_MAX_TRACKS or K + tracks.shape[nl + 1] > SE3MPC_MAX_SPHERES or self.be.suffix(tracks) != suf):
+            raise ValueError(f"tracks: expected {tuple(lead) + (N,)} + (Kt<={SE3MPC_MAX_TRACKS}, 4) {suf} with K + Kt <= {SE3MPC_MAX_SPHERES}, "
+                             f"got {tuple(tracks.shape)}")
+        return tracks.shape[nl + 1]
 
     @staticmethod
     def _B(ld: int, B: Optional[int]) -> int:
@@ -443,15 +453,21 @@ class Ops:
         return self._same(U, p0, v0, goal if params.has_goal else None), U.shape[1]
 
     def _mppi_call(self, base, tail, params, p0, v0, goal, U, n_samples, iters, sigma, temperature, seed, iter_base, index_base, spheres,
-                   obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out, sphere_vel=None, sphere_t0=0.0):
+                   obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out, sphere_vel=None, sphere_t0=0.0, tracks=None):
         """The operand checks, output allocation and call shared by :meth:`mppi` and :meth:`mppi_split`; ``tail``: the arguments between
-        ``keys`` and ``stream``; ``sphere_vel``: the moving entry's two arguments go in after ``spheres``."""
+        ``keys`` and ``stream``; ``sphere_vel``: the moving entry's two arguments go in after ``spheres``; ``tracks``: (N, Kt, 4) or
+        (ld, N, Kt, 4), the tracks entry's three arguments go in after ``K``."""
         suf, ld = self._mppi_operands(params, U, p0, v0, goal)
         N = params.horizon
         K = 0
         if spheres is not None:
             K = self._spheres(spheres, suf)
         motion = () if sphere_vel is None else self._sphere_vel(sphere_vel, sphere_t0, K, suf)
+        slab = ()
+        if tracks is not None:
+            per_problem = getattr(tracks, "ndim", 0) == 4
+            Kt = self._tracks(tracks, (ld,) if per_problem else (), N, K, suf)
+            slab = (self.be.ptr(tracks if Kt else None), Kt, 4 * N * Kt if per_problem else 0)
         if out is not None:
             U_out, cost, trace, keys = out
         else:
@@ -462,7 +478,7 @@ class Ops:
         self.lib.call(base, suf, self._B(ld, B), ld, int(n_samples), int(iters), float(sigma), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
                       int(iter_base) & 0xFFFFFFFF, self.be.ptr(iter_offset), int(index_base) & 0xFFFFFFFF, self.be.ptr(p0), self.be.ptr(v0),
                       self.be.ptr(goal if params.has_goal else None), self.be.ptr(U), self.be.ptr(U_out), self.be.ptr(spheres if K else None), *motion, K,
-                      float(obstacle_weight), self.be.ptr(cost), self.be.ptr(trace), self.be.ptr(keys), *tail, self.be.stream(),
+                      *slab, float(obstacle_weight), self.be.ptr(cost), self.be.ptr(trace), self.be.ptr(keys), *tail, self.be.stream(),
                       params=params)
         return dict(U=U_out, cost=cost, trace=trace if (trace is None or iters > 0) else trace[:0], keys=keys)
 
@@ -483,6 +499,21 @@ class Ops:
                                    index_base, spheres, obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out, sphere_vel, sphere_t0)
         return self._mppi_call("mppi", (), params, p0, v0, goal, U, n_samples, iters, sigma, temperature, seed, iter_base,
                                index_base, spheres, obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out)
+
+    def mppi_tracks(self, params: Params, p0, v0, goal, U, n_samples: int, iters: int, sigma: float, temperature: float, tracks, seed: int = 0,
+                    iter_base: int = 0, index_base: int = 0, spheres=None, obstacle_weight: float = 0.0, U_out=None, want_trace: bool = True,
+                    want_keys: bool = True, iter_offset=None, B: Optional[int] = None, out=None, sphere_vel=None, sphere_t0: float = 0.0):
+        """``se3mpc_mppi_tracks_*``: :meth:`mppi` around moving spheres (sphere_vel None: they stand still) and, behind them, spheres with a
+        predicted path.  tracks: (N, Kt, 4) rows (x, y, z, r) shared by all problems, or (ld, N, Kt, 4) one slab per problem, same dtype:
+        row [k][j] is tracked sphere j at the time of the state before step k (sphere_t0 + k dt on the table's clock).  Kt = 0 is the
+        moving entry.  -> the dict of :meth:`mppi`."""
+        suf = self.be.suffix(U)
+        K = 0 if spheres is None else spheres.shape[0]
+        if sphere_vel is None:
+            sphere_vel = self.be.empty((K, 3), suf)
+            sphere_vel[...] = 0.0
+        return self._mppi_call("mppi_tracks", (), params, p0, v0, goal, U, n_samples, iters, sigma, temperature, seed, iter_base, index_base,
+                               spheres, obstacle_weight, U_out, want_trace, want_keys, iter_offset, B, out, sphere_vel, sphere_t0, tracks)
 
     def mppi_split_workspace(self, params: Params, nprob: int, splits: int):
         """A workspace for :meth:`mppi_split` over `nprob` problems (float64 words; no initialisation needed)."""
@@ -749,7 +780,7 @@ class Ops:
                          cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
                          seed: int = 0, cycle_base: int = 0, shift: int = 1, iter_base: int = 0, index_base: int = 0, spheres=None,
                          obstacle_weight: float = 0.0, wind=None, want_trace: bool = True, want_plan: bool = False, clearance=None,
-                         want_clearance: bool = True, sphere_vel=None, sphere_t0: float = 0.0):
+                         want_clearance: bool = True, sphere_vel=None, sphere_t0: float = 0.0, tracks=None):
         """se3mpc_mppi_closed_loop_*: `cycles` x (`iters` MPPI iterations from the drone's own state on its nominal, the plan handed to the
         controller on the chip, `substeps` control + simulator steps, the nominal shifted by `shift` rows) for B drones in ONE launch, in
         place on (state, time, pos, vel, att, omega) and on the nominals U (B, N, 3).  goal (B, 3); spheres (K, 4) rows (cx, cy, cz, r)
@@ -759,7 +790,9 @@ class Ops:
         plan_last (B, 3, N, 3) = P, V, A of the last cycle's plan | None, clearance (B,) | None).
         sphere_vel: None, or (K, 3) rows (vx, vy, vz): the spheres move with constant velocity (``se3mpc_mppi_closed_loop_moving_*``);
         sphere_t0: the time of the RUN's start (cycle 0) after the time the table holds, the same in every chained call -- plan and
-        clearance take the centres at the time of the step they look at."""
+        clearance take the centres at the time of the step they look at.
+        tracks: None, or (cycles, B, N, Kt, 4) rows (x, y, z, r): spheres with a predicted path behind the moving ones, renewed every cycle
+        (``se3mpc_mppi_closed_loop_tracks_*``, see :meth:`mppi_closed_loop_tracks`)."""
         B = pos.shape[0]
         suf = self.be.suffix(pos)
         N = params.horizon
@@ -781,34 +814,74 @@ class Ops:
         trace = self.be.empty((B, max(int(cycles), 1), max(int(iters), 1)), suf) if want_trace else None
         plan = self.be.empty((B, 3, N, 3), suf) if want_plan else None
         motion = () if sphere_vel is None else self._sphere_vel(sphere_vel, sphere_t0, K, suf)
-        self.lib.loop_call("mppi_closed_loop" if sphere_vel is None else "mppi_closed_loop_moving", suf, params, cp, sp, B, int(cycles), int(substeps), float(sim_dt), int(cycle_base) & 0xFFFFFFFF,
+        slab = ()
+        if tracks is not None:
+            if sphere_vel is None:
+                raise ValueError("tracks come behind a moving table: pass sphere_vel (zeros for spheres that stand still)")
+            Kt = self._tracks(tracks, (max(int(cycles), 0), B), N, K, suf)
+            slab = (self.be.ptr(tracks if Kt else None), Kt)
+        self.lib.loop_call("mppi_closed_loop_tracks" if tracks is not None else "mppi_closed_loop" if sphere_vel is None else "mppi_closed_loop_moving", suf, params, cp, sp, B, int(cycles), int(substeps), float(sim_dt), int(cycle_base) & 0xFFFFFFFF,
                            int(shift), int(n_samples), int(iters), float(sigma), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF,
                            int(iter_base) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF, self.be.ptr(goal), self.be.ptr(spheres if K else None), *motion, K,
-                           float(obstacle_weight), self.be.ptr(wind), w_stride, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel),
+                           *slab, float(obstacle_weight), self.be.ptr(wind), w_stride, self.be.ptr(time), self.be.ptr(pos), self.be.ptr(vel),
                            self.be.ptr(att), self.be.ptr(omega), self.be.ptr(state), self.be.ptr(U), self.be.ptr(cost), self.be.ptr(trace),
                            self.be.ptr(plan), self.be.ptr(clearance), self.be.stream())
         if trace is not None and (cycles <= 0 or iters <= 0):
             trace = trace[:, :max(int(cycles), 0), :max(int(iters), 0)]
         return dict(U=U, cost=cost, trace=trace, plan_last=plan, clearance=clearance)
 
-    def mppi_swarm_workspace(self, B: int, suf: str):
+    def mppi_closed_loop_tracks(self, params: Params, cp: ControllerParams, sp: SimulatorParams, state, time, pos, vel, att, omega, goal, U,
+                                cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float, tracks,
+                                spheres=None, sphere_vel=None, **kw):
+        """se3mpc_mppi_closed_loop_tracks_*: :meth:`mppi_closed_loop` around moving spheres (sphere_vel None: they stand still) and, behind
+        them, Kt spheres with a predicted path.  tracks (cycles, B, N, Kt, 4) rows (x, y, z, r): cycle c of the call of drone b plans around
+        slab [c][b], whose row [k][j] is sphere j at the time of the state before step k of that cycle's plan.  The clearance sees the
+        moving rows only.  Every other argument and the result are :meth:`mppi_closed_loop`'s."""
+        if sphere_vel is None:
+            K = 0 if spheres is None else spheres.shape[0]
+            sphere_vel = self.be.empty((K, 3), self.be.suffix(pos))
+            sphere_vel[...] = 0.0
+        return self.mppi_closed_loop(params, cp, sp, state, time, pos, vel, att, omega, goal, U, cycles, substeps, sim_dt, n_samples, iters, sigma,
+                                     temperature, spheres=spheres, sphere_vel=sphere_vel, tracks=tracks, **kw)
+
+    def mppi_swarm_workspace(self, B: int, suf: str, horizon: Optional[int] = None):
         """A workspace for :meth:`mppi_closed_loop_swarm` over `B` drones of dtype `suf` ("f32" / "f64"): the two snapshot images (no
-        initialisation needed)."""
+        initialisation needed).  horizon: that of the plans, for ``share_plans=True`` (the images carry the intents too)."""
         esz = {"f32": 4, "f64": 8}[suf]
-        return self.be.empty((max(self.lib.mppi_swarm_workspace_bytes(int(B), esz) // esz, 1),), suf)
+        need = self.lib.mppi_swarm_workspace_bytes(int(B), esz) if horizon is None else self.lib.mppi_swarm_intent_workspace_bytes(int(B), int(horizon), esz)
+        return self.be.empty((max(need // esz, 1),), suf)
+
+    def swarm_intent(self, params: Params, pos, vel, U, intent=None):
+        """se3mpc_swarm_intent_*: the intent of every drone, (B, N, 3): row [b][k] = the position before step k of the nominal U (B, N, 3)
+        rolled out from (pos, vel) (B, 3) with the plan's recurrence -- what a drone shows its mates under ``share_plans=True``."""
+        B, N = pos.shape[0], params.horizon
+        suf = self.be.suffix(pos)
+        for nm, a, shape in (("pos", pos, (B, 3)), ("vel", vel, (B, 3)), ("U", U, (B, N, 3)), ("intent", intent, (B, N, 3))):
+            if a is None:
+                continue
+            self.be.check(a, nm)
+            if tuple(a.shape) != shape or self.be.suffix(a) != suf:
+                raise ValueError(f"{nm}: expected {shape} {suf}, got {tuple(a.shape)}")
+        if intent is None:
+            intent = self.be.empty((B, N, 3), suf)
+        self.lib.loop_call("swarm_intent", suf, params, B, self.be.ptr(pos), self.be.ptr(vel), self.be.ptr(U), self.be.ptr(intent), self.be.stream())
+        return intent
 
     def mppi_closed_loop_swarm(self, params: Params, cp: ControllerParams, sp: SimulatorParams, state, time, pos, vel, att, omega, goal, U,
                                cycles: int, substeps: int, sim_dt: float, n_samples: int, iters: int, sigma: float, temperature: float,
                                swarm_size: int = 1, neighbours: int = 0, mate_radius: float = 0.0, seed: int = 0, cycle_base: int = 0,
                                shift: int = 1, iter_base: int = 0, index_base: int = 0, spheres=None, obstacle_weight: float = 0.0, wind=None,
                                want_trace: bool = True, want_plan: bool = False, clearance=None, want_clearance: bool = True, sphere_vel=None,
-                               sphere_t0: float = 0.0, separation=None, want_neighbours: bool = False, workspace=None):
+                               sphere_t0: float = 0.0, separation=None, want_neighbours: bool = False, workspace=None, share_plans: bool = False):
         """se3mpc_mppi_closed_loop_swarm_*: :meth:`mppi_closed_loop` around moving spheres for B / `swarm_size` swarms of `swarm_size`
         drones, every drone planning around its `neighbours` nearest swarm-mates as spheres of radius `mate_radius` that fly on with the
         velocity they have when the cycle starts; one launch per cycle plus a seed, all enqueued by one call.  spheres / sphere_vel: the
         shared table (K, 4) / (K, 3) (sphere_vel None: the spheres stand still).  separation: a (B,) running minimum to continue, or None: a
         fresh one at +inf; it takes the distance to the nearest mate at every cycle's start (:meth:`swarm_separation` adds the state as it
         stands).  workspace: a tensor of :meth:`mppi_swarm_workspace` to reuse (required under graph capture); None allocates one.
+        share_plans: the mates are shown as their PLANS (``se3mpc_mppi_closed_loop_swarm_intent_*``): every drone publishes the rollout of
+        its nominal beside its snapshot row and a mate's sphere is where that rollout puts it at every step of the horizon, not where its
+        velocity points; `neighbours` <= SE3MPC_MAX_TRACKS, and a workspace of ``mppi_swarm_workspace(B, suf, horizon)``.
         -> the dict of :meth:`mppi_closed_loop` plus separation (B,) and neighbours (B, `neighbours`) int32 | None: the drones chosen in
         the last cycle, rank order, -1 in unused slots."""
         B = pos.shape[0]
@@ -838,7 +911,7 @@ class Ops:
         Kn = int(neighbours)
         esz = {"f32": 4, "f64": 8}[suf]
         if workspace is None:
-            workspace = self.mppi_swarm_workspace(B, suf)
+            workspace = self.mppi_swarm_workspace(B, suf, N if share_plans else None)
         else:
             self.be.check(workspace, "workspace")
             if self.be.suffix(workspace) != suf:
@@ -849,7 +922,7 @@ class Ops:
         nb = self.be.empty((B, max(Kn, 1)), "i32") if want_neighbours else None
         if nb is not None:
             nb[...] = -1
-        self.lib.loop_call("mppi_closed_loop_swarm", suf, params, cp, sp, B, int(swarm_size), Kn, float(mate_radius), int(cycles), int(substeps),
+        self.lib.loop_call("mppi_closed_loop_swarm_intent" if share_plans else "mppi_closed_loop_swarm", suf, params, cp, sp, B, int(swarm_size), Kn, float(mate_radius), int(cycles), int(substeps),
                            float(sim_dt), int(cycle_base) & 0xFFFFFFFF, int(shift), int(n_samples), int(iters), float(sigma), float(temperature),
                            int(seed) & 0xFFFFFFFFFFFFFFFF, int(iter_base) & 0xFFFFFFFF, int(index_base) & 0xFFFFFFFF, self.be.ptr(goal),
                            self.be.ptr(spheres if K else None), *motion, K, float(obstacle_weight), self.be.ptr(wind), w_stride, self.be.ptr(time),

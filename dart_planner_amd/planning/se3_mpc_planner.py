@@ -16,6 +16,7 @@ starts of one problem and returns the best -- restart 0 is always the reference'
 """
 from __future__ import annotations
 
+import functools
 import logging
 import math
 import ctypes
@@ -84,6 +85,7 @@ class SE3MPCPlanner(BasePlanner):
         self.goal_position: Optional[np.ndarray] = None
         self.obstacles: List[Tuple[np.ndarray, float]] = []
         self.moving_obstacles: List[Tuple[np.ndarray, float, np.ndarray, float]] = []      # (centre, radius, velocity, timestamp)
+        self.tracked_obstacles: List[Tuple[np.ndarray, np.ndarray, float]] = []            # (times (n,), centres (n, 3), radius)
         # planner.py:158-159.  The reference never assigns last_solution, so its warm start
         # (_create_warm_start, :294-327) is dead code and every solve is a cold start.  With
         # receding_horizon=True this planner does what that code intended: it keeps the last solution
@@ -152,9 +154,40 @@ class SE3MPCPlanner(BasePlanner):
         v = np.array(to_float(velocity), dtype=float).reshape(3)
         self.moving_obstacles.append((c, r, v, float(timestamp)))
 
+    def add_tracked_obstacle(self, times, centres, radius) -> None:
+        """A sphere with a PREDICTED PATH -- a pedestrian track, another vehicle's published trajectory: its centre is `centres[i]` (n, 3) at
+        `times[i]` (n,), rising, on the clock of ``DroneState.timestamp``; linear in between, held at both ends.  :meth:`plan_mppi` and
+        :meth:`plan_batch_mppi` resample the polyline on the host, in float64, at the plan's step times and penalise every step of the horizon
+        against the centre at that step (``se3mpc_mppi_tracks_*``; at most SE3MPC_MAX_TRACKS = 16 of them).  The other
+        planning paths and the constraint helpers do not see tracked obstacles."""
+        t = np.asarray(to_float(times), dtype=float).reshape(-1)
+        c = np.array(ensure_units(centres, "m", "SE3MPCPlanner.add_tracked_obstacle centres"), dtype=float).reshape(-1, 3)
+        r = float(ensure_units(radius, "m", "SE3MPCPlanner.add_tracked_obstacle radius"))
+        if len(t) < 1 or len(t) != len(c) or np.any(np.diff(t) <= 0) or not (np.all(np.isfinite(t)) and np.all(np.isfinite(c))):
+            raise ValueError("add_tracked_obstacle: times must be (n,) finite and strictly rising, centres (n, 3) finite, n >= 1")
+        self.tracked_obstacles.append((t, c, r))
+
+    def _tracked_obstacle_slab(self, obstacles, now: float) -> Optional[np.ndarray]:
+        """(N, Kt, 4) rows (x, y, z, r) for the entries of tracked spheres: row [k][j] = tracked obstacle j at the plan's step k, i.e. k * dt
+        seconds after `now` (the state's timestamp).  The polyline's times are rebased to `now` in float64 first, as
+        :meth:`_moving_obstacle_table` rebases centres, then sampled linearly, held at both ends.  None when there is none, or when
+        `obstacles` names a table of its own (or False)."""
+        if not self.tracked_obstacles or not (obstacles is None or obstacles is True):
+            return None
+        N, dt = self.se3_config.prediction_horizon, self.se3_config.dt
+        tau = np.arange(N, dtype=float) * dt
+        slab = np.empty((N, len(self.tracked_obstacles), 4))
+        for j, (t, c, r) in enumerate(self.tracked_obstacles):
+            rel = t - float(now)
+            for a in range(3):
+                slab[:, j, a] = np.interp(tau, rel, c[:, a])
+            slab[:, j, 3] = r
+        return slab
+
     def clear_obstacles(self) -> None:
         self.obstacles.clear()
         self.moving_obstacles.clear()
+        self.tracked_obstacles.clear()
 
     def sense(self, current_state: DroneState, goal_position):
         goal_position = ensure_units(goal_position, "m", "SE3MPCPlanner.sense goal_position")
@@ -597,6 +630,8 @@ class SE3MPCPlanner(BasePlanner):
         one launch per iteration and one more; n_samples must be a multiple of 64 * splits); "auto" = n_samples // 256, and the one-launch
         path where that is 1.
         The split plan differs from the unsplit one in the last bits of its float64 sums only (``splits`` = 1: not at all).
+        Tracked obstacles (:meth:`add_tracked_obstacle`) take the same eager path through ``se3mpc_mppi_tracks_*``, the planner's whole
+        table as its moving rows (zero velocities where nothing moves); ``splits`` raises there too.
         Moving obstacles (:meth:`add_moving_obstacle`, or an ``obstacles`` array of (K, 7) rows (cx, cy, cz, r, vx, vy, vz) holding at the
         state's timestamp): with at least one non-zero velocity the plan is ``se3mpc_mppi_moving_*`` on the table rebased to the state's
         timestamp (:meth:`_moving_obstacle_table`), launch by launch -- the EAGER path even on a graph-capable backend, since the rebased
@@ -617,8 +652,14 @@ class SE3MPCPlanner(BasePlanner):
         splits = self._mppi_splits(splits, n_samples)
         if moving is not None and splits is not None:
             raise ValueError("plan_mppi: the split form is not built for moving obstacles (se3mpc_mppi_moving_* has no split entry): use splits=None")
+        slab = self._tracked_obstacle_slab(obstacles, current_state.timestamp)
+        if slab is not None and splits is not None:
+            raise ValueError("plan_mppi: the split form is not built for tracked obstacles (se3mpc_mppi_tracks_* has no split entry): use splits=None")
         args = (ops, prm, p0, v0, U0, int(n_samples), int(iters), float(sigma), float(temperature), int(seed), precision, sph, w_obs, it_base, splits)
-        if moving is not None:
+        if slab is not None:                                          # the tracked rows come behind the whole table, moving or not
+            tab = self._moving_obstacle_table(obstacles, current_state.timestamp)
+            r, trace = self._plan_mppi_eager(*args, moving=np.zeros((0, 7)) if tab is None else tab, tracks=slab)
+        elif moving is not None:
             r, trace = self._plan_mppi_eager(*args, moving=moving)
         elif getattr(ops.be, "graph_capable", False):
             r, trace = self._plan_mppi_captured(*args)
@@ -642,10 +683,11 @@ class SE3MPCPlanner(BasePlanner):
         return np.ascontiguousarray(tab[:, :4]), (tab if np.any(tab[:, 4:] != 0.0) else None)
 
     def _plan_mppi_eager(self, ops, prm, p0, v0, U0, n_samples, iters, sigma, temperature, seed, precision, sph, w_obs, it_base, splits=None,
-                         moving=None):
+                         moving=None, tracks=None):
         """plan_mppi launch by launch (any backend): -> (packed float64 result of se3mpc_shooting_finish_*, trace).  moving: the (K, 7)
         table of :meth:`_moving_obstacle_table` -- ``se3mpc_mppi_moving_*`` with sphere_t0 = 0, the finish without spheres and the packed
-        (cost, penalty, cost_with_penalty) completed from the MPPI entry's own cost."""
+        (cost, penalty, cost_with_penalty) completed from the MPPI entry's own cost.  tracks: the (N, Kt, 4) slab of
+        :meth:`_tracked_obstacle_slab` behind that table (``se3mpc_mppi_tracks_*``)."""
         N = prm.horizon
         be = ops.be
         suf = "f32" if precision == "f32" else "f64"
@@ -654,8 +696,10 @@ class SE3MPCPlanner(BasePlanner):
         if moving is not None:
             npdt = np.float32 if suf == "f32" else np.float64
             dev = lambda a: be.from_host(np.ascontiguousarray(a.astype(npdt)))
-            out = ops.mppi(prm, col(p0, suf), col(v0, suf), col(self.goal_position, suf), col(U0, suf), n_samples, iters, sigma, temperature, seed=seed,
-                           iter_base=it_base, spheres=dev(moving[:, :4]), obstacle_weight=w_obs, sphere_vel=dev(moving[:, 4:]), sphere_t0=0.0)
+            tables = dict(spheres=dev(moving[:, :4]) if len(moving) else None, sphere_vel=dev(moving[:, 4:]) if len(moving) else None, sphere_t0=0.0)
+            entry = ops.mppi if tracks is None else functools.partial(ops.mppi_tracks, tracks=dev(tracks))
+            out = entry(prm, col(p0, suf), col(v0, suf), col(self.goal_position, suf), col(U0, suf), n_samples, iters, sigma, temperature, seed=seed,
+                        iter_base=it_base, obstacle_weight=w_obs, **tables)
             res = be.empty((19 * N + 3,), "f64")
             ops.shooting_finish(prm, out["U"], out["keys"], state, res)
             r = np.asarray(be.to_host(res), dtype=float).copy()
@@ -741,7 +785,9 @@ class SE3MPCPlanner(BasePlanner):
         nominal (B, N, 3) or None = hover.  Returns arrays with a leading B axis: positions, velocities, thrust_vectors, accelerations,
         attitudes, body_rates (B, N, 3), thrusts (B, N), cost (B,) with the penalty, trace (B, iters).  ``splits`` as :meth:`plan_mppi`; "auto"
         also keeps B * splits within 1024 workgroups.  Moving obstacles as :meth:`plan_mppi`: ``timestamp`` is the time all B states hold
-        (rebasing the planner's own moving obstacles); with a non-zero velocity the launch is ``se3mpc_mppi_moving_*`` and ``splits`` raises."""
+        (rebasing the planner's own moving obstacles); with a non-zero velocity the launch is ``se3mpc_mppi_moving_*`` and ``splits`` raises.
+        Tracked obstacles (:meth:`add_tracked_obstacle`) are resampled at `timestamp` and shared by all B problems (one slab,
+        ``se3mpc_mppi_tracks_*``); ``splits`` raises."""
         p0 = np.asarray(to_float(positions), float).reshape(-1, 3)
         v0 = np.asarray(to_float(velocities), float).reshape(-1, 3)
         g = np.asarray(to_float(goals), float).reshape(-1, 3)
@@ -762,9 +808,17 @@ class SE3MPCPlanner(BasePlanner):
             if self._mppi_splits(splits, n_samples, B) is not None:
                 raise ValueError("plan_batch_mppi: the split form is not built for moving obstacles: use splits=None")
             more = dict(sphere_vel=be.from_host(np.ascontiguousarray(moving[:, 4:].astype(npdt))), sphere_t0=0.0)
-        out = self._mppi_op(ops, self._mppi_splits(splits, n_samples, B), prm, lp0, lv0, lg, lane(U), n_samples, iters, sigma, temperature, seed=seed,
-                            iter_base=iter_base, spheres=None if sph is None else be.from_host(np.ascontiguousarray(sph.astype(npdt))),
-                            obstacle_weight=w_obs, want_keys=False, **more)
+        slab = self._tracked_obstacle_slab(obstacles, timestamp)
+        sph_d = None if sph is None else be.from_host(np.ascontiguousarray(sph.astype(npdt)))
+        if slab is not None:
+            if self._mppi_splits(splits, n_samples, B) is not None:
+                raise ValueError("plan_batch_mppi: the split form is not built for tracked obstacles: use splits=None")
+            vel = None if sph is None else be.from_host(np.ascontiguousarray(self._moving_obstacle_table(obstacles, timestamp)[:, 4:].astype(npdt)))
+            out = ops.mppi_tracks(prm, lp0, lv0, lg, lane(U), n_samples, iters, sigma, temperature, be.from_host(np.ascontiguousarray(slab.astype(npdt))),
+                                  seed=seed, iter_base=iter_base, spheres=sph_d, obstacle_weight=w_obs, want_keys=False, sphere_vel=vel, sphere_t0=0.0)
+        else:
+            out = self._mppi_op(ops, self._mppi_splits(splits, n_samples, B), prm, lp0, lv0, lg, lane(U), n_samples, iters, sigma, temperature, seed=seed,
+                                iter_base=iter_base, spheres=sph_d, obstacle_weight=w_obs, want_keys=False, **more)
         _, _, P, V = ops.rollout_cost_grad(prm, lp0, lv0, lg, out["U"], want_grad=False, want_states=True)
         acc, att, rates, thr = ops.extract(prm, out["U"])
         h = lambda a, shape: np.asarray(be.to_host(a), dtype=float).T.reshape(shape).copy()

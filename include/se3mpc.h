@@ -41,6 +41,7 @@ extern "C" {
 #define SE3MPC_MAX_CORRECTIONS 10  /* L-BFGS memory m (SciPy default maxcor = 10)          */
 #define SE3MPC_MAX_SPHERES 256     /* obstacle table staged in LDS (4 KB)                  */
 #define SE3MPC_MAX_SWARM 1024      /* drones per swarm (se3mpc_mppi_closed_loop_swarm_*)   */
+#define SE3MPC_MAX_TRACKS 16       /* tracked spheres (se3mpc_mppi_tracks_*): an LDS slab [N][Kt][4] */
 
 enum se3mpc_status {
   SE3MPC_OK = 0,
@@ -363,6 +364,27 @@ int se3mpc_mppi_moving_f64(const se3mpc_params* p, int nprob, int ld, int S, int
                            uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const double* p0, const double* v0,
                            const double* goal, const double* U_in, double* U_out, const double* spheres, const double* sphere_vel,
                            double sphere_t0, int K, double obstacle_weight, double* cost, double* trace, uint64_t* keys, void* stream);
+/* se3mpc_mppi_moving_* around spheres with a PREDICTED PATH as well: an obstacle whose centre is given per step of the
+ * horizon -- a pedestrian track, another vehicle's published trajectory -- not as c + v t.  The operands of se3mpc_mppi_moving_*, and
+ * after K: tracks, device [N][Kt][4] = (x, y, z, radius) per problem, same type; Kt in [0, SE3MPC_MAX_TRACKS] with K + Kt <=
+ * SE3MPC_MAX_SPHERES; track_stride, in elements between the slabs of consecutive problems (0: one slab for all; otherwise >= 4 N Kt).
+ * Row [k][j] is tracked sphere j at the time of the state before step k -- the instant tau_k of se3mpc_mppi_moving_* -- so the penalty of
+ * step k walks the K moving rows exactly as se3mpc_mppi_moving_* does and then the Kt rows [k][.] in rising j with the same expression
+ * dz^2 + (dy^2 + (dx^2 - (r + margin)^2)) and no time arithmetic; the penalties add up in that order.  The slab is staged once per launch
+ * (N = 64, Kt = 16 in float64: 32 KB of LDS).  Kt = 0 reads no slab and gives se3mpc_mppi_moving_*'s outputs bit for bit; Kt tracks that
+ * hold one centre at every step give those of se3mpc_mppi_moving_* on K + Kt rows whose last Kt velocities are zero.
+ * Checks: those of se3mpc_mppi_moving_* with the same codes, then Kt outside [0, SE3MPC_MAX_TRACKS], K + Kt > SE3MPC_MAX_SPHERES or a
+ * track_stride that is neither 0 nor >= 4 N Kt: SE3MPC_ERR_SHAPE; tracks NULL with Kt > 0: SE3MPC_ERR_NULL.  There is no split form. */
+int se3mpc_mppi_tracks_f32(const se3mpc_params* p, int nprob, int ld, int S, int iters, double sigma, double temperature, uint64_t seed,
+                           uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const float* p0, const float* v0,
+                           const float* goal, const float* U_in, float* U_out, const float* spheres, const float* sphere_vel, double sphere_t0,
+                           int K, const float* tracks, int Kt, long long track_stride, double obstacle_weight, float* cost, float* trace,
+                           uint64_t* keys, void* stream);
+int se3mpc_mppi_tracks_f64(const se3mpc_params* p, int nprob, int ld, int S, int iters, double sigma, double temperature, uint64_t seed,
+                           uint32_t iter_base, const uint32_t* iter_offset, uint32_t index_base, const double* p0, const double* v0,
+                           const double* goal, const double* U_in, double* U_out, const double* spheres, const double* sphere_vel,
+                           double sphere_t0, int K, const double* tracks, int Kt, long long track_stride, double obstacle_weight, double* cost,
+                           double* trace, uint64_t* keys, void* stream);
 /* se3mpc_mppi_* with ONE problem's samples split over `splits` workgroups (split j owns samples [j S / splits, (j + 1) S / splits)), for
  * the call that plans one or a few problems and would otherwise run on one or a few compute units.  Same operands, same noise (the
  * counter (q, s, g, k) does not depend on who draws a sample), same cost, same update, same outputs as se3mpc_mppi_*; only the order of
@@ -985,6 +1007,28 @@ int se3mpc_mppi_closed_loop_moving_f64(const se3mpc_params* p, const se3mpc_cont
                                        double* omega, double* state, double* U, double* cost, double* trace, double* plan_last,
                                        double* clearance, void* stream);
 
+/* se3mpc_mppi_closed_loop_moving_* with the tracked spheres of se3mpc_mppi_tracks_* (DESIGN.md 5.8h): the operands of
+ * se3mpc_mppi_closed_loop_moving_*, and after K: tracks, device [cycles][B][N][Kt][4] = (x, y, z, radius), and Kt.  Predictions are renewed
+ * every cycle: cycle c of the CALL (0 <= c < cycles, whatever cycle_base is) of drone b plans around slab [c][b], whose row [k][j] is
+ * sphere j at the time of the state before step k of that cycle's plan.  The in-flight clearance is measured against the K moving rows
+ * only: a track is a prediction at plan steps, not a surface at simulator steps.  Kt = 0 gives se3mpc_mppi_closed_loop_moving_*'s
+ * outputs bit for bit.  Checks: those of se3mpc_mppi_closed_loop_moving_*, then Kt outside [0, SE3MPC_MAX_TRACKS] or K + Kt >
+ * SE3MPC_MAX_SPHERES: SE3MPC_ERR_SHAPE; tracks NULL with Kt > 0: SE3MPC_ERR_NULL. */
+int se3mpc_mppi_closed_loop_tracks_f32(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B,
+                                       int cycles, int substeps, double sim_dt, uint32_t cycle_base, int shift, int S, int iters, double sigma,
+                                       double temperature, uint64_t seed, uint32_t iter_base, uint32_t index_base, const float* goal,
+                                       const float* spheres, const float* sphere_vel, double sphere_t0, int K, const float* tracks, int Kt,
+                                       double obstacle_weight, const float* wind, long long wind_stride, double* time, float* pos, float* vel,
+                                       float* att, float* omega, double* state, float* U, float* cost, float* trace, float* plan_last,
+                                       float* clearance, void* stream);
+int se3mpc_mppi_closed_loop_tracks_f64(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B,
+                                       int cycles, int substeps, double sim_dt, uint32_t cycle_base, int shift, int S, int iters, double sigma,
+                                       double temperature, uint64_t seed, uint32_t iter_base, uint32_t index_base, const double* goal,
+                                       const double* spheres, const double* sphere_vel, double sphere_t0, int K, const double* tracks, int Kt,
+                                       double obstacle_weight, const double* wind, long long wind_stride, double* time, double* pos, double* vel,
+                                       double* att, double* omega, double* state, double* U, double* cost, double* trace, double* plan_last,
+                                       double* clearance, void* stream);
+
 /* se3mpc_mppi_closed_loop_moving_* for SWARMS: the B drones of a call are B / swarm_size swarms of M = swarm_size drones
  * (drone b belongs to swarm b / M; its mates are the other drones of that swarm), and every drone plans around its nearest mates as
  * spheres of radius mate_radius that move with constant velocity.  The operands are those of se3mpc_mppi_closed_loop_moving_*, same
@@ -1042,6 +1086,43 @@ int se3mpc_mppi_closed_loop_swarm_f64(const se3mpc_params* p, const se3mpc_contr
                                       long long wind_stride, double* time, double* pos, double* vel, double* att, double* omega, double* state,
                                       double* U, double* cost, double* trace, double* plan_last, double* clearance, double* separation,
                                       int32_t* neighbours, void* workspace, size_t workspace_bytes, void* stream);
+
+/* se3mpc_mppi_closed_loop_swarm_* with SHARED PLANS: a drone sees where its mates intend to go, not where their
+ * velocities point.  The operands, the selection (d2, eligibility, ranks), separation, neighbours and every guarantee are those of
+ * se3mpc_mppi_closed_loop_swarm_*; what differs is the table.  A drone's INTENT at a cycle's start is its nominal U as the cycle finds it
+ * (shifted by the cycle before) rolled out from its (pos, vel) with the plan's recurrence: N rows, row k = the position before step k,
+ * the instants the penalty of that cycle looks at.  The mate of rank r fills tracked row r of se3mpc_mppi_closed_loop_tracks_* -- centre
+ * [k][r] = row k of its intent, radius mate_radius -- instead of moving row K + r, so one call equals, per cycle and per drone,
+ * se3mpc_swarm_intent_* on the call's (pos, vel, U), then se3mpc_mppi_closed_loop_tracks_* with B = 1, index_base = b, cycle_base = C, one
+ * cycle, the shared table as its K moving rows and Kt = Kn_eff, bit for bit.  The snapshot carries the intents: every workgroup reads one
+ * image and writes its new (pos, vel) and its new intent to the other; the kernel boundary stays the only synchronisation.  The call
+ * seeds the first image from (pos, vel, U) itself (two small launches, then one per cycle), so chained calls need nothing carried over.
+ * workspace: at least se3mpc_mppi_swarm_intent_workspace_bytes(B, params->horizon, sizeof(R)) bytes = 2 x B x (6 + 3 N) elements (0 for
+ * B < 0, a horizon outside [1, SE3MPC_MAX_HORIZON] or an elem_size that is not 4 or 8).  Argument rules: those of
+ * se3mpc_mppi_closed_loop_swarm_* with the same codes, and neighbours_k > SE3MPC_MAX_TRACKS: SE3MPC_ERR_SHAPE. */
+size_t se3mpc_mppi_swarm_intent_workspace_bytes(int B, int horizon, int elem_size);
+int se3mpc_mppi_closed_loop_swarm_intent_f32(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B,
+                                             int swarm_size, int neighbours_k, double mate_radius, int cycles, int substeps, double sim_dt,
+                                             uint32_t cycle_base, int shift, int S, int iters, double sigma, double temperature, uint64_t seed,
+                                             uint32_t iter_base, uint32_t index_base, const float* goal, const float* spheres,
+                                             const float* sphere_vel, double sphere_t0, int K, double obstacle_weight, const float* wind,
+                                             long long wind_stride, double* time, float* pos, float* vel, float* att, float* omega, double* state,
+                                             float* U, float* cost, float* trace, float* plan_last, float* clearance, float* separation,
+                                             int32_t* neighbours, void* workspace, size_t workspace_bytes, void* stream);
+int se3mpc_mppi_closed_loop_swarm_intent_f64(const se3mpc_params* p, const se3mpc_controller_params* cp, const se3mpc_simulator_params* sp, int B,
+                                             int swarm_size, int neighbours_k, double mate_radius, int cycles, int substeps, double sim_dt,
+                                             uint32_t cycle_base, int shift, int S, int iters, double sigma, double temperature, uint64_t seed,
+                                             uint32_t iter_base, uint32_t index_base, const double* goal, const double* spheres,
+                                             const double* sphere_vel, double sphere_t0, int K, double obstacle_weight, const double* wind,
+                                             long long wind_stride, double* time, double* pos, double* vel, double* att, double* omega,
+                                             double* state, double* U, double* cost, double* trace, double* plan_last, double* clearance,
+                                             double* separation, int32_t* neighbours, void* workspace, size_t workspace_bytes, void* stream);
+/* The intent of every drone (one lane each): intent [B][N][3], row [b][k] = the position before step k of the nominal U [B][N][3] rolled
+ * out from (pos, vel) [B][3] with the plan's recurrence (the P rows of plan_last of se3mpc_mppi_closed_loop_* at that U, bit for bit).
+ * The seed of a run of se3mpc_mppi_closed_loop_swarm_intent_*.  params NULL or a NULL operand with B > 0: SE3MPC_ERR_NULL; invalid
+ * params: the code of se3mpc_check_params; B < 0: SE3MPC_ERR_SHAPE; B = 0 is a no-op. */
+int se3mpc_swarm_intent_f32(const se3mpc_params* p, int B, const float* pos, const float* vel, const float* U, float* intent, void* stream);
+int se3mpc_swarm_intent_f64(const se3mpc_params* p, int B, const double* pos, const double* vel, const double* U, double* intent, void* stream);
 
 /* The distance of every drone to its nearest eligible swarm-mate as (pos, vel) [B][3] stand: separation[b] = min(separation[b],
  * (R)sqrt(min d2)) with d2, eligibility and the E = 0 rule of se3mpc_mppi_closed_loop_swarm_*.  Reads pos and vel, writes separation only.
